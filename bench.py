@@ -7,7 +7,22 @@ scene (every iteration until the reference's termination rule), with the rays
 resident in HBM when the timed region starts (lpc_trace_reset restores them
 device-to-device).  value = ray-bounces of all ranks / max-over-ranks time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--rays R] [--no-cpu] [--no-configs]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--rays R] [--dump-outputs DIR]
+                    [--full [--no-cpu] [--no-configs] [--no-strong] [--no-prof]]
+
+A plain run does what the headline figure needs and no more: it builds the scene
+and the rays, warms up, times the K steps (no HIP events in the timed region),
+writes the last timed step's outputs when --dump-outputs is given, and prints
+the result line (metric, value, unit, higher_is_better, dtype, ms_per_step, the
+per-rank times, steps_identical).  Everything below "With --full" is measured
+or checked only with --full, whose timed region carries the walk kernel's HIP
+events for the roofline figures (--no-prof leaves them out).
+
+--dump-outputs DIR writes what the last timed step returned to its caller
+(ShardedTrace.run's result on rank 0) as DIR/<name>.npy, float64: mesh_power
+(per-mesh measured power), global_counts (rays entering each iteration),
+ray_bounces and iterations.  The rays and the scene are seeded, so two runs with
+the same arguments trace identical inputs.
 
 Multi-GPU: run under torch.distributed.run (the driver's form), or directly with
 --gpus N > 1, when the parent starts torch.distributed.run with N ranks as a child
@@ -19,7 +34,7 @@ on the stats all-reduced over the ranks of the node through the library's
 shared-memory hook (lpc_set_allreduce + lpc_shm_allreduce); the trace-end
 histogram and the timing go over RCCL (torch.distributed "nccl").
 
-The line also carries:
+With --full the line also carries:
   strong        strong scaling: ONE fixed global set of --rays rays (seed 7, the
                 N=1 headline's rays) split over the ranks with shard_bounds, traced
                 to the global termination; per-rank ms, global counts;
@@ -103,6 +118,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rays", type=int, default=1_000_000, help="rays per GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (what ShardedTrace.run returned) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg: first-iteration parity, HIP events and roofline, the "
+                         "one-engine figure, histogram, strong / config-5 blocks, CPU baseline, configs 2-4, "
+                         "cold and fresh-rays blocks (the --no-* options leave legs of --full out)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline / parity leg")
     ap.add_argument("--cpu-rays", type=int, default=1 << 20, help="CPU baseline sample (rays, one bounce)")
     ap.add_argument("--no-configs", action="store_true", help="skip BASELINE configs 2-4")
@@ -114,7 +135,19 @@ def parse():
     ap.add_argument("--inflight", type=int, default=int(os.environ.get("LPC_BENCH_INFLIGHT", 3)),
                     help="traces in flight per GPU: engines (handles, each its own stream) tracing the "
                          "workload's rays from their own host threads (1: one engine, traces back to back)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+def dump_outputs(path, r):
+    """The last timed step's result (ShardedTrace.run's dict) as float64 .npy files."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "mesh_power.npy"), np.asarray(r["mesh_power"], np.float64).reshape(-1))
+    np.save(os.path.join(path, "global_counts.npy"), np.asarray(r["global_counts"], np.float64).reshape(-1))
+    np.save(os.path.join(path, "ray_bounces.npy"), np.asarray([r["bounces"]], np.float64))
+    np.save(os.path.join(path, "iterations.npy"), np.asarray([r["iterations"]], np.float64))
 
 
 def src_sha16():
@@ -671,15 +704,18 @@ def main():
             raise errs[0]
         return [r for rs in out for r in rs]
 
-    # the first iteration alone, for the parity leg (same stats the timed trace starts with)
-    eng.reset()
-    st0, _ = eng.iterate()
-    first = {"stats": st0, "population": p}
-    eng.sync()
+    full = a.full
+    first = None
+    if full:
+        # the first iteration alone, for the parity leg (same stats the timed trace starts with)
+        eng.reset()
+        st0, _ = eng.iterate()
+        first = {"stats": st0, "population": p}
+        eng.sync()
     for j in range(E):
         for _ in range(a.warmup):
             step(j)
-    if not a.no_prof:
+    if full and not a.no_prof:
         # HIP events around the walk kernel's launches only (created without the
         # system-scope fence, which cost ~7 us per launch; PROF_EVERY > 1 samples
         # every k-th launch), on every engine
@@ -703,10 +739,12 @@ def main():
     for e in engines:
         e.prof_enable(False)
     steps_identical = all(x == results[0] for x in results)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, res[-1])
     # the same steps on one engine, back to back (the per-trace time without
     # overlap; beside the headline, not a separate workload)
     seq = None
-    if E > 1:
+    if full and E > 1:
         eng.set_walk_grid(0)                    # one trace alone: the library default
         for _ in range(3):
             step(0)
@@ -730,14 +768,17 @@ def main():
         seq = {"ray_bounces_per_s": bs / dts, "ms_per_step": dts / a.steps * 1e3, "steps": a.steps,
                "identical_to_inflight": all((r["global_counts"], [float(x) for x in r["mesh_power"]]) == results[0]
                                             for r in rs)}
-    # trace-end histogram over RCCL (the north star's all-reduce), outside the timed region
-    eng.reset()
-    hr = runner.run(sc.iterations, sc.tau, in_pow, hist=(sc.hist_limits, sc.hist_points),
-                    input_power_global=in_pow_all)
-    hist_total = float(np.sum(hr["hist"][0]) * ((sc.hist_limits[0][1] - sc.hist_limits[0][0]) / sc.hist_points) ** 2)
+    hr = hist_total = None
+    if full:
+        # trace-end histogram over RCCL (the north star's all-reduce), outside the timed region
+        eng.reset()
+        hr = runner.run(sc.iterations, sc.tau, in_pow, hist=(sc.hist_limits, sc.hist_points),
+                        input_power_global=in_pow_all)
+        hist_total = float(np.sum(hr["hist"][0])
+                           * ((sc.hist_limits[0][1] - sc.hist_limits[0][0]) / sc.hist_points) ** 2)
     dev = ("cpu" if rehearse else f"cuda:{local}") if dist else None
     blocks = {}
-    if not a.no_strong:
+    if full and not a.no_strong:
         from lightpycl_amd.distributed import shard_bounds
         # strong scaling: the N=1 headline's global rays (seed 7), one shard per rank
         # (sc: the same scene and trace parameters as the weak block)
@@ -795,7 +836,7 @@ def main():
     achieved = alg_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
     pairs_per_s = bounces_all * M / dt                   # reference-equivalent RI/s (sum N_iter * M / T)
     mt_tflops = pairs_per_s * MT_FLOPS / 1e12
-    pmc = load_pmc()
+    pmc = load_pmc() if full else {}
     stale = pmc.get("stale", True)
     traffic = None if stale else pmc.get("hbm_bytes_per_launch")
     valu_per_launch = None if stale else pmc.get("sq_insts_valu_mean")
@@ -878,8 +919,13 @@ def main():
         "hist_total_power": hist_total,
         "cpu_baseline": None,
     }
+    out["full"] = bool(full)
+    if not full:
+        # these take the legs of --full (HIP events, the exchange timing, the histogram trace)
+        for k in ("roofline", "roofline_valu", "exchange", "hist_total_power"):
+            del out[k]
     par = {"steps_identical": bool(steps_identical)}
-    if not a.no_cpu:
+    if full and not a.no_cpu:
         # N=1: the timed CPU baseline and the bitwise check on the same oracle outputs;
         # N>1: rank 0 checks a 20k-ray sample of its shard (untimed)
         nr = a.cpu_rays if world == 1 else 20000
@@ -894,8 +940,9 @@ def main():
         out["config5"] = dict(blocks["config5"], scaling="strong",
                               workload=f"BASELINE config 5: {a.c5_rays} synthetic rays as {C5_BLOCKS} blocks "
                                        f"(seeds 7..{6 + C5_BLOCKS}) over {world} rank(s)")
-    out["weak_global_counts"] = [int(x) for x in hr["global_counts"]]
-    if world == 1 and not a.no_configs:
+    if full:
+        out["weak_global_counts"] = [int(x) for x in hr["global_counts"]]
+    if world == 1 and full and not a.no_configs:
         for r_ in runners:
             r_.close()
         for e in engines:

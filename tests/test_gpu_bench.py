@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-ARGS = ["--steps", "5", "--warmup", "1", "--no-cpu", "--no-configs", "--rays", "200000", "--strong-steps", "5",
+ARGS = ["--full", "--steps", "5", "--warmup", "1", "--no-cpu", "--no-configs", "--rays", "200000", "--strong-steps", "5",
         "--c5-rays", "1600000", "--c5-steps", "2"]
 
 
@@ -62,7 +62,7 @@ def test_bench_gpus2_launches_two_ranks():
     assert one["strong"]["global_counts"] == one["weak_global_counts"]
 
 
-ARGS8 = ["--steps", "3", "--warmup", "1", "--no-cpu", "--no-configs", "--rays", "40000", "--strong-steps", "3",
+ARGS8 = ["--full", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-configs", "--rays", "40000", "--strong-steps", "3",
          "--c5-rays", "320000", "--c5-steps", "1"]
 
 
@@ -82,3 +82,32 @@ def test_bench_gpus8_rehearsal():
         assert a["global_counts"] == b["global_counts"], (blk, a["global_counts"], b["global_counts"])
         assert len(a["rank_ray_bounces_per_step"]) == 8
         assert sum(a["rank_ray_bounces_per_step"]) == pytest.approx(b["rank_ray_bounces_per_step"][0], rel=1e-12)
+
+
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times --steps traces and stops there: the line
+    carries the headline fields and none of the legs of --full, and
+    --dump-outputs writes the last timed step's outputs as float64 .npy files
+    that a second run with the same arguments reproduces bit for bit."""
+    import numpy as np
+    args = ["--steps", "4", "--warmup", "1", "--rays", "50000"]
+    a = _bench(1, args + ["--dump-outputs", str(tmp_path / "a")])
+    b = _bench(1, args + ["--dump-outputs", str(tmp_path / "b")])
+    assert a["full"] is False and a["steps"] == 4 and a["warmup"] == 1
+    assert a["unit"] == "ray-bounces/s" and a["higher_is_better"] is True and a["dtype"] == "f32"
+    assert a["value"] > 0 and a["ms_per_step"] > 0
+    assert a["parity"] == {"steps_identical": True}
+    for k in ("roofline", "roofline_valu", "exchange", "strong", "config5", "configs", "cold", "fresh_rays",
+              "hist_total_power", "weak_global_counts"):
+        assert k not in a, k
+    assert a["cpu_baseline"] is None and a["inflight"]["sequential"] is None
+    names = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert names == ["global_counts.npy", "iterations.npy", "mesh_power.npy", "ray_bounces.npy"]
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float64 and x.ndim == 1 and x.size > 0
+        assert np.array_equal(x, y), n
+    counts = np.load(tmp_path / "a" / "global_counts.npy")
+    assert counts[0] == 50000 and counts.sum() == np.load(tmp_path / "a" / "ray_bounces.npy")[0]
+    assert len(counts) == np.load(tmp_path / "a" / "iterations.npy")[0]
+    assert np.load(tmp_path / "a" / "mesh_power.npy").sum() > 0

@@ -20,7 +20,7 @@ fresh) LPC_HOSTPROF=${HP:-0} run 300 fresh.json python -u tools/fresh_probe.py ;
 stream) run 600 pytest_stream.log python -u -m pytest -x -v --timeout 300 --timeout-method thread -m gpu tests/test_gpu_stream.py ;;
 dispatch) run 120 dispatch.json tools/_dispatch_probe ;;
 quick) run 300 quick.json python -u bench.py --no-cpu --no-configs --no-strong ;;
-bench) run 900 bench.json python -u bench.py ;;
+bench) run 900 bench.json python -u bench.py --full ;;
 ab) AB_STEPS=${AB_STEPS:-300} run 900 ab.log python -u tools/ab.py ${AB_REPS:-3} $AB_CFGS ;;
 abcfg) run 900 abcfg.log python -u tools/ab_cfg.py $ABCFG_ARGS ;;
 stats) run 300 stats_synth.log python -u tools/trace_stats.py synthetic 1000000
@@ -30,7 +30,7 @@ kt) prof 300 --kernel-trace --stats -d $R/$O/kt -o kt --output-format csv -- pyt
     python tools/kt_timeline.py $O/kt 60 > $O/timeline.txt; python tools/kt_steps.py $O/kt > $O/steps.txt ;;
 ktstats) prof 300 --kernel-trace --stats -d $R/$O/kts -o kts --output-format csv -- python3 $R/bench.py --steps 20 --warmup 2 --no-cpu --no-configs --no-strong > $O/kts.log 2>&1 || { echo ktstats failed; exit 1; } ;;
 pmcwalk) for grp in "$PMC1" "$PMC2" "$PMC3"; do [ -z "$grp" ] && continue; tag=$(echo $grp | md5sum | cut -c1-6)
-      ( cd /tmp && export TMPDIR=/tmp && timeout -s KILL 120 rocprofv3 --pmc $grp -d $R/$O/pmc_$tag -o pmc --output-format csv -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu --no-configs --no-strong > $R/$O/pmc_$tag.log 2>&1 ) || { echo "pmc $grp failed"; exit 1; }
+      ( cd /tmp && export TMPDIR=/tmp && timeout -s KILL 120 rocprofv3 --pmc $grp -d $R/$O/pmc_$tag -o pmc --output-format csv -- python3 $R/bench.py --full --steps 1 --warmup 0 --no-cpu --no-configs --no-strong > $R/$O/pmc_$tag.log 2>&1 ) || { echo "pmc $grp failed"; exit 1; }
       echo "$grp" > $O/pmc_$tag.groups; done ;;
 esac; done
 exit 0
