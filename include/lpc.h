@@ -286,6 +286,46 @@ int lpc_project_hist(lpc_handle *h, int mode, int64_t n, const float *pos4, cons
                      const double *yedges, int ny, double weight_div, double *H,
                      float *x, float *y, float *pwr_cor);
 
+/* ---- beam analysis: elevation passes (iterative_tracer.py:420-501) -------- */
+/* The elevation of a point against `pole` (double[4]) is what numpy evaluates for
+ * arccos(dot(pos / norm(pos, axis=1), pole)) on float32 (n,4) rows: float32 norm
+ * and division, float64 dot and acos (lpc_math.hpp elevation).  A point whose
+ * elevation is not finite (zero position, non-unit pole) is invalid: counted and
+ * left out of every sum.  The sort key of a valid point is the bit pattern of its
+ * elevation (uint64, monotone since e >= 0).  Every pass takes n host points
+ * pos4 (n,4) + pwr[n], or with pos4 == NULL the trace's device-resident measured
+ * record (w = 0), recomputes the elevations, runs on the handle's stream and is
+ * synchronised before it returns; its outputs are small host arrays, sums in
+ * float64 (atomic order, so the last bits vary from call to call). */
+typedef struct {
+    int64_t n_valid;         /* points with a finite elevation                   */
+    int64_t n_invalid;       /* the others                                        */
+    int64_t n_negative;      /* valid points whose power is < 0 or NaN            */
+    double e_min, e_max;     /* over the valid points (NaN when there are none)   */
+    double total_power;      /* float64 sum of the valid points' power            */
+} lpc_elev_summary;
+int lpc_elev_scan(lpc_handle *h, int64_t n, const float *pos4, const float *pwr, const double *pole,
+                  lpc_elev_summary *out);
+/* np.histogram-compatible binning of the elevations, weights (double)pwr, into
+ * H[nbins] over the float64 edges[nbins+1] (value == last edge goes to the last
+ * bin, outside -> dropped).  elev_out (may be NULL): the elevations, float64[n],
+ * NaN for an invalid point. */
+int lpc_elev_hist(lpc_handle *h, int64_t n, const float *pos4, const float *pwr, const double *pole,
+                  const double *edges, int nbins, double *H, double *elev_out);
+/* One pass of a radix descent over the keys, 1 <= bits <= 12: over the valid
+ * points with key >> (shift + bits) == prefix (every valid point when
+ * shift + bits == 64), bin (key >> shift) & ((1 << bits) - 1) accumulates
+ * bin_pow (power), bin_cnt (points) and bin_maxkey (largest key, 0 for an empty
+ * bin); each array has 1 << bits entries. */
+int lpc_elev_digit_pass(lpc_handle *h, int64_t n, const float *pos4, const float *pwr, const double *pole,
+                        uint64_t prefix, int shift, int bits, double *bin_pow, int64_t *bin_cnt,
+                        uint64_t *bin_maxkey);
+/* Power and count of the valid points with elevation < thr (<= thr when
+ * inclusive != 0) and the largest such elevation (NaN when there is none).
+ * Outputs may be NULL. */
+int lpc_elev_power_below(lpc_handle *h, int64_t n, const float *pos4, const float *pwr, const double *pole,
+                         double thr, int inclusive, double *power, int64_t *count, double *e_max);
+
 /* ---- diagnostics ---------------------------------------------------------- */
 /* The device's own conservative-filter code on n (ray, record) pairs, host
  * arrays: origin3/dir3 (n,3), rec5 (n,5) = centre xyz, negB, negA (filter_record /

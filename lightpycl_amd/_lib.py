@@ -28,6 +28,11 @@ class IterStats(ctypes.Structure):
                 ("power_next", ctypes.c_double), ("power_nonneg", ctypes.c_int64)]
 
 
+class ElevSummary(ctypes.Structure):
+    _fields_ = [("n_valid", ctypes.c_int64), ("n_invalid", ctypes.c_int64), ("n_negative", ctypes.c_int64),
+                ("e_min", ctypes.c_double), ("e_max", ctypes.c_double), ("total_power", ctypes.c_double)]
+
+
 class Prof(ctypes.Structure):
     _fields_ = [("intersect_ms", ctypes.c_double), ("shade_ms", ctypes.c_double),
                 ("intersect_launches", ctypes.c_int64), ("pairs", ctypes.c_int64),
@@ -86,6 +91,10 @@ _PROTOS = {
     "lpc_set_walk_grid": [_P, _I64],
     "lpc_project_hist": [_P, _INT, _I64, _P, _P, _P, _P, _P, _INT, _P, _INT, _F64, _P, _P, _P,
                          _P],
+    "lpc_elev_scan": [_P, _I64, _P, _P, _P, _P],
+    "lpc_elev_hist": [_P, _I64, _P, _P, _P, _P, _INT, _P, _P],
+    "lpc_elev_digit_pass": [_P, _I64, _P, _P, _P, ctypes.c_uint64, _INT, _INT, _P, _P, _P],
+    "lpc_elev_power_below": [_P, _I64, _P, _P, _P, _F64, _INT, _P, _P, _P],
     "lpc_prof_enable": [_P, _INT],
     "lpc_prof_read": [_P, _P, _INT],
     "lpc_filter_eval": [_P, _I64, _P, _P, _P, _INT, _P],

@@ -324,6 +324,45 @@ struct ProjArgs {
     double *H;
 };
 
+// Elevation analyses (k_elev_*): the points and the pole, then one pass's own
+// arguments.  Points: pos4 rows (host points, w as given) or the measured
+// record's px/py/pz (w = 0).
+struct ElevIn {
+    int64_t n;
+    const float4 *pos4;
+    const float *px, *py, *pz, *pwr;
+    double pole[4];
+};
+struct ElevScanOut {                  // zeroed before the launch except emin_bits = ~0
+    unsigned long long n_valid, n_invalid, n_negative;
+    unsigned long long emin_bits, emax_bits;
+    double total;
+};
+struct ElevHistArgs {
+    ElevIn in;
+    const double *edges;
+    int nbins;
+    double *H;
+    double *elev_out;                 // optional, [n]
+};
+struct ElevDigitArgs {
+    ElevIn in;
+    unsigned long long prefix;
+    int shift, bits, all;             // all: shift + bits == 64, every valid ray
+    double *bin_pow;
+    unsigned long long *bin_cnt, *bin_maxkey;
+};
+struct ElevBelowOut {
+    double power;
+    unsigned long long count, emax_bits;
+};
+struct ElevBelowArgs {
+    ElevIn in;
+    double thr;
+    int inclusive;
+    ElevBelowOut *out;
+};
+
 // set_rays' analysis of the emitted rays (k_ray_scan), read back once.
 struct RayScan {
     unsigned long long dmax2_bits;    // max |D|^2 (float64, NaN as +inf): the bits of a non-negative double

@@ -25,6 +25,11 @@
 //                    :366-373), measured-ray record and float64 power sums.
 //   k_project_hist   angular/stereographic projection (.cl:488-538) and
 //                    np.histogram2d-compatible binning (iterative_tracer.py:534-562).
+//   k_elev_scan/k_elev_hist/k_elev_digit/k_elev_below
+//                    the beam analyses' passes over the measured record
+//                    (iterative_tracer.py:420-501): elevation range and totals,
+//                    np.histogram-compatible binning, one radix pass of the
+//                    half-power selection, power below an elevation.
 // Layout in HBM: SoA float/int32 arrays per ray; triangle records AoS (32 B
 // filter record, 48 B exact record, 36 B vertices), see DESIGN.md.
 #include <hip/hip_runtime.h>
@@ -2385,6 +2390,211 @@ __global__ __launch_bounds__(256) void k_mesh_sum(int64_t n, const float *__rest
     if (lane == 0) s[wv] = acc;
     __syncthreads();
     if (threadIdx.x == 0) out[blockIdx.x] = ((s[0] + s[1]) + s[2]) + s[3];
+}
+
+// ---------------------------------------------------------------------------
+// Elevation analyses of the measured record (iterative_tracer.py:420-501 on the
+// device): every pass recomputes a ray's elevation (lpc_math.hpp elevation) from
+// its 16 B and keeps nothing per ray.  Grid-stride over 256-ray rows.  k_elev_scan,
+// k_elev_hist and k_elev_below loop on a per-thread bound (lanes leave at different
+// iterations) and reduce over the wave only AFTER the loop, where the wave has
+// reconverged: no shuffle, ballot or any_lane may move inside those loops.  Only
+// k_elev_digit, which reduces per iteration, loops on a block-uniform bound with
+// the tail lanes masked by `i < n`.
+static __device__ __forceinline__ unsigned long long wave_umin(unsigned long long v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { const unsigned long long t = __shfl_xor(v, o, 64); v = t < v ? t : v; }
+    return v;
+}
+static __device__ __forceinline__ unsigned long long wave_umax(unsigned long long v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { const unsigned long long t = __shfl_xor(v, o, 64); v = t > v ? t : v; }
+    return v;
+}
+static __device__ __forceinline__ unsigned long long wave_usum(unsigned long long v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// Elevation and power of ray i; false (e = NaN) for an invalid ray.
+static __device__ __forceinline__ bool elev_load(const ElevIn &A, int64_t i, double &e, float &pw)
+{
+    float x, y, z, w = 0.0f;
+    if (A.pos4) { const float4 v = A.pos4[i]; x = v.x; y = v.y; z = v.z; w = v.w; }
+    else { x = A.px[i]; y = A.py[i]; z = A.pz[i]; }
+    pw = A.pwr[i];
+    e = elevation(x, y, z, w, A.pole);
+    return e == e;
+}
+
+__global__ __launch_bounds__(256) void k_elev_scan(ElevIn A, ElevScanOut *out)
+{
+    __shared__ double s_p[4];
+    __shared__ unsigned long long s_c[4][5];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    unsigned long long nv = 0, ni = 0, nn = 0, kmin = ~0ull, kmax = 0ull;
+    double tot = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < A.n; i += stride) {
+        double e;
+        float pw;
+        if (elev_load(A, i, e, pw)) {
+            const unsigned long long k = elev_key(e);
+            nv += 1;
+            nn += !(pw >= 0.0f);
+            kmin = k < kmin ? k : kmin;
+            kmax = k > kmax ? k : kmax;
+            tot += (double)pw;
+        } else ni += 1;
+    }
+    nv = wave_usum(nv); ni = wave_usum(ni); nn = wave_usum(nn);
+    kmin = wave_umin(kmin); kmax = wave_umax(kmax);
+    tot = wave_sum(tot);
+    if (lane == 0) { s_p[wv] = tot; s_c[wv][0] = nv; s_c[wv][1] = ni; s_c[wv][2] = nn; s_c[wv][3] = kmin; s_c[wv][4] = kmax; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; ++k) {
+            nv += s_c[k][0]; ni += s_c[k][1]; nn += s_c[k][2];
+            kmin = s_c[k][3] < kmin ? s_c[k][3] : kmin;
+            kmax = s_c[k][4] > kmax ? s_c[k][4] : kmax;
+        }
+        if (ni) atomicAdd(&out->n_invalid, ni);
+        if (nv) {
+            atomicAdd(&out->n_valid, nv);
+            if (nn) atomicAdd(&out->n_negative, nn);
+            atomicMin(&out->emin_bits, kmin);
+            atomicMax(&out->emax_bits, kmax);
+            atomicAdd(&out->total, ((s_p[0] + s_p[1]) + s_p[2]) + s_p[3]);
+        }
+    }
+}
+
+// H[b] += (double)pwr over the valid rays, bins by bin_of.  LDS: the block's
+// bins in shared memory (nbins <= LPC_ELEV_LDS_BINS), flushed once; otherwise
+// global atomics per ray, as k_project_hist.
+#define LPC_ELEV_LDS_BINS 4096
+template <bool LDS>
+__global__ __launch_bounds__(256) void k_elev_hist(ElevHistArgs A)
+{
+    __shared__ double sh[LDS ? LPC_ELEV_LDS_BINS : 1];
+    if (LDS) {
+        for (int b = threadIdx.x; b < A.nbins; b += 256) sh[b] = 0.0;
+        __syncthreads();
+    }
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < A.in.n; i += stride) {
+        double e;
+        float pw;
+        const bool ok = elev_load(A.in, i, e, pw);
+        if (A.elev_out) A.elev_out[i] = e;
+        if (!ok) continue;
+        const int b = bin_of(e, A.edges, A.nbins);
+        if (b < 0) continue;
+        if (LDS) atomicAdd(&sh[b], (double)pw);
+        else atomicAdd(&A.H[b], (double)pw);
+    }
+    if (LDS) {
+        __syncthreads();
+        for (int b = threadIdx.x; b < A.nbins; b += 256)
+            if (sh[b] != 0.0) atomicAdd(&A.H[b], sh[b]);         // (a NaN sum compares unequal too)
+    }
+}
+
+// One pass of the radix descent over the elevation keys: the valid rays whose
+// key >> (shift + bits) equals prefix, binned by their next `bits` bits: power,
+// count and largest key per bin.  NB = 1 << bits rounded up to 2048 or 4096 bins
+// in LDS (20 B each).  In the early passes a wave's rays mostly share one bin
+// (the exponent bits of an angle): such a wave reduces in registers and issues
+// one LDS atomic per array instead of 64 on one address.
+template <int NB>
+__global__ __launch_bounds__(256) void k_elev_digit(ElevDigitArgs A)
+{
+    __shared__ double s_pow[NB];
+    __shared__ unsigned long long s_max[NB];
+    __shared__ uint32_t s_cnt[NB];
+    const int nb = 1 << A.bits;
+    for (int b = threadIdx.x; b < nb; b += 256) { s_pow[b] = 0.0; s_max[b] = 0ull; s_cnt[b] = 0u; }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const unsigned long long mask = (unsigned long long)(nb - 1);
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < A.in.n; base += stride) {
+        const int64_t i = base + threadIdx.x;
+        bool sel = false;
+        unsigned long long key = 0ull;
+        float pw = 0.0f;
+        if (i < A.in.n) {
+            double e;
+            if (elev_load(A.in, i, e, pw)) {
+                key = elev_key(e);
+                sel = A.all || (key >> (A.shift + A.bits)) == A.prefix;
+            }
+        }
+        const uint64_t m = __ballot(sel);
+        if (m == 0) continue;
+        const int b = (int)((key >> A.shift) & mask);
+        const int first = __ffsll((unsigned long long)m) - 1;
+        const int b0 = __shfl(b, first, 64);
+        if (!any_lane(sel && b != b0)) {
+            const double p = wave_sum(sel ? (double)pw : 0.0);
+            const unsigned long long k = wave_umax(sel ? key : 0ull);
+            if (lane == 0) {
+                atomicAdd(&s_pow[b0], p);
+                atomicAdd(&s_cnt[b0], (uint32_t)__popcll((unsigned long long)m));
+                atomicMax(&s_max[b0], k);
+            }
+        } else if (sel) {
+            atomicAdd(&s_pow[b], (double)pw);
+            atomicAdd(&s_cnt[b], 1u);
+            atomicMax(&s_max[b], key);
+        }
+    }
+    __syncthreads();
+    for (int b = threadIdx.x; b < nb; b += 256)
+        if (s_cnt[b]) {
+            atomicAdd(&A.bin_pow[b], s_pow[b]);
+            atomicAdd(&A.bin_cnt[b], (unsigned long long)s_cnt[b]);
+            atomicMax(&A.bin_maxkey[b], s_max[b]);
+        }
+}
+
+// Power, count and largest elevation of the valid rays with e < thr (e <= thr
+// when inclusive).
+__global__ __launch_bounds__(256) void k_elev_below(ElevBelowArgs A)
+{
+    __shared__ double s_p[4];
+    __shared__ unsigned long long s_c[4][2];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    unsigned long long cnt = 0, kmax = 0ull;
+    double tot = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < A.in.n; i += stride) {
+        double e;
+        float pw;
+        if (!elev_load(A.in, i, e, pw)) continue;
+        if (A.inclusive ? e <= A.thr : e < A.thr) {
+            const unsigned long long k = elev_key(e);
+            cnt += 1;
+            kmax = k > kmax ? k : kmax;
+            tot += (double)pw;
+        }
+    }
+    cnt = wave_usum(cnt);
+    kmax = wave_umax(kmax);
+    tot = wave_sum(tot);
+    if (lane == 0) { s_p[wv] = tot; s_c[wv][0] = cnt; s_c[wv][1] = kmax; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; ++k) { cnt += s_c[k][0]; kmax = s_c[k][1] > kmax ? s_c[k][1] : kmax; }
+        if (cnt) {
+            atomicAdd(&A.out->power, ((s_p[0] + s_p[1]) + s_p[2]) + s_p[3]);
+            atomicAdd(&A.out->count, cnt);
+            atomicMax(&A.out->emax_bits, kmax);
+        }
+    }
 }
 
 }  // namespace lpck

@@ -16,6 +16,7 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -332,6 +333,37 @@ LPC_HD void stereograph_project(f3 p, f3 piv, f3 R0, f3 R1, f3 R2, float pwr, fl
     float q = 1.0f + xt * xt + yt * yt;
     float A = 4.0f / (q * q);
     x = xt; y = yt; pc = pwr / A;
+}
+
+// ---------------------------------------------------------------------------
+// Elevation of a measured position against a pole, as the beam analyses
+// (iterative_tracer.py:420-501) evaluate it with numpy on float32 (n,4) rows and a
+// float64 pole: arccos(dot(pos / norm(pos, axis=1), pole)).
+//   nrm = sqrt(((x x + y y) + z z) + w w)   every operation rounded to float32
+//   u   = pos / nrm                         IEEE float32 division
+//   c   = ((u0 p0 + u1 p1) + u2 p2) + u3 p3 float64, no FMA, summed from +0
+// The products u_k p_k of an axis-aligned pole are exact, so c is numpy's bit for
+// bit whatever order its dot takes; e = acos(c) is as close to numpy's as the two
+// acos implementations are.  A zero row gives 0/0 = NaN, a
+// non-unit pole |c| > 1: e is NaN and the ray is invalid.
+LPC_HD double elev_cos(float x, float y, float z, float w, const double *p)
+{
+    LPC_EXACT
+    const float xx = x * x, yy = y * y, zz = z * z, ww = w * w;
+    const float s = ((xx + yy) + zz) + ww;
+    const float nrm = sqrtf(s);
+    const float u0 = x / nrm, u1 = y / nrm, u2 = z / nrm, u3 = w / nrm;
+    const double t0 = (double)u0 * p[0], t1 = (double)u1 * p[1], t2 = (double)u2 * p[2], t3 = (double)u3 * p[3];
+    return (((0.0 + t0) + t1) + t2) + t3;   // numpy's dot accumulates from +0: four -0 terms give +0
+}
+LPC_HD double elevation(float x, float y, float z, float w, const double *p) { return acos(elev_cos(x, y, z, w, p)); }
+// The sort key of an elevation: its bit pattern, monotone for e >= 0 (acos never
+// returns -0).  NaN (invalid) is tested by the caller before the key is used.
+LPC_HD uint64_t elev_key(double e)
+{
+    uint64_t k;
+    memcpy(&k, &e, 8);
+    return k;
 }
 
 // ---------------------------------------------------------------------------

@@ -3109,6 +3109,179 @@ int lpc_project_hist(lpc_handle *h, int mode, int64_t n, const float *pos4, cons
     return 0;
 }
 
+// ---- elevation analyses (iterative_tracer.py:420-501) -------------------------
+// Every lpc_elev_* entry point goes: NULL-handle check, settle, its own argument
+// checks, then elev_begin: the points (host points uploaded behind `head` bytes
+// of pass scratch in d_tmp, or the measured record) and the pole.  *scratch = the
+// head region (256-B aligned).
+static int elev_begin(lpc_handle *h, const char *who, int64_t &n, const float *pos4, const float *pwr,
+                      const double *pole, size_t head, ElevIn &in, char **scratch)
+{
+    if (!pole) return set_err(h, LPC_E_ARG, std::string(who) + ": pole is NULL");
+    if (pos4 && !pwr) return set_err(h, LPC_E_ARG, std::string(who) + ": pwr is NULL");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!pos4) n = h->m_total;
+    if (n < 0) return set_err(h, LPC_E_ARG, std::string(who) + ": negative n");
+    head = (head + 255) / 256 * 256;
+    RETIF(dalloc(h, h->d_tmp, head + (pos4 ? (size_t)n * 20 : 0) + 16));
+    char *d = (char *)h->d_tmp.p;
+    memset(&in, 0, sizeof(in));
+    in.n = n;
+    if (pos4) {
+        if (n > 0) {
+            HIPCHK(h, hipMemcpy(d + head, pos4, (size_t)n * 16, hipMemcpyHostToDevice));
+            HIPCHK(h, hipMemcpy(d + head + (size_t)n * 16, pwr, (size_t)n * 4, hipMemcpyHostToDevice));
+        }
+        in.pos4 = (const float4 *)(d + head);
+        in.pwr = (const float *)(d + head + (size_t)n * 16);
+    } else {
+        const size_t mc = (size_t)h->m_cap;
+        const float *mf = (const float *)h->m_buf.p;
+        in.px = mf; in.py = mf + mc; in.pz = mf + 2 * mc; in.pwr = mf + 3 * mc;
+    }
+    for (int k = 0; k < 4; ++k) in.pole[k] = pole[k];
+    *scratch = d;
+    return 0;
+}
+// Grid of the grid-stride elevation kernels: enough blocks to fill the GPU
+// (per_cu blocks per CU), never more than the rows.
+static inline unsigned elev_grid(const lpc_handle *h, int64_t n, int per_cu)
+{
+    const int64_t cap = (int64_t)std::max(h->cus, 1) * per_cu;
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, cap));
+}
+static inline double bits_to_double(unsigned long long b)
+{
+    double v;
+    memcpy(&v, &b, 8);
+    return v;
+}
+
+int lpc_elev_scan(lpc_handle *h, int64_t n, const float *pos4, const float *pwr, const double *pole,
+                  lpc_elev_summary *out)
+{
+    if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
+    RETIF(settle(h));                   // a trace still running (lpc_trace_iterate / _run_async)
+    if (!out) return set_err(h, LPC_E_ARG, "elev_scan: out is NULL");
+    ElevIn in;
+    char *d = nullptr;
+    RETIF(elev_begin(h, "elev_scan", n, pos4, pwr, pole, sizeof(ElevScanOut), in, &d));
+    ElevScanOut z;
+    memset(&z, 0, sizeof(z));
+    z.emin_bits = ~0ull;
+    HIPCHK(h, hipMemcpy(d, &z, sizeof(z), hipMemcpyHostToDevice));
+    if (n > 0) {
+        hipLaunchKernelGGL(k_elev_scan, dim3(elev_grid(h, n, 8)), dim3(256), 0, h->stream, in, (ElevScanOut *)d);
+        HIPCHK(h, hipGetLastError());
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(&z, d, sizeof(z), hipMemcpyDeviceToHost));
+    out->n_valid = (int64_t)z.n_valid;
+    out->n_invalid = (int64_t)z.n_invalid;
+    out->n_negative = (int64_t)z.n_negative;
+    out->e_min = z.n_valid ? bits_to_double(z.emin_bits) : NAN;
+    out->e_max = z.n_valid ? bits_to_double(z.emax_bits) : NAN;
+    out->total_power = z.total;
+    return 0;
+}
+
+int lpc_elev_hist(lpc_handle *h, int64_t n, const float *pos4, const float *pwr, const double *pole,
+                  const double *edges, int nbins, double *H, double *elev_out)
+{
+    if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
+    RETIF(settle(h));                   // h->m_total below is the finished trace's
+    if (nbins <= 0 || !edges || !H) return set_err(h, LPC_E_ARG, "elev_hist: bad argument");
+    ElevIn in;
+    char *d = nullptr;
+    // scratch: [edges | H | elev_out (one double per point: n, or the record's length)]
+    const int64_t n_out = elev_out ? (pos4 ? n : (int64_t)h->m_total) : 0;
+    const size_t o_H = ((size_t)(nbins + 1) * 8 + 255) / 256 * 256;
+    const size_t o_e = (o_H + (size_t)nbins * 8 + 255) / 256 * 256;
+    RETIF(elev_begin(h, "elev_hist", n, pos4, pwr, pole, o_e + (size_t)std::max<int64_t>(n_out, 0) * 8, in, &d));
+    HIPCHK(h, hipMemcpy(d, edges, (size_t)(nbins + 1) * 8, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemsetAsync(d + o_H, 0, (size_t)nbins * 8, h->stream));
+    ElevHistArgs A;
+    A.in = in;
+    A.edges = (const double *)d;
+    A.nbins = nbins;
+    A.H = (double *)(d + o_H);
+    A.elev_out = elev_out ? (double *)(d + o_e) : nullptr;
+    if (n > 0) {
+        if (nbins <= LPC_ELEV_LDS_BINS)
+            hipLaunchKernelGGL(k_elev_hist<true>, dim3(elev_grid(h, n, 8)), dim3(256), 0, h->stream, A);
+        else
+            hipLaunchKernelGGL(k_elev_hist<false>, dim3(elev_grid(h, n, 8)), dim3(256), 0, h->stream, A);
+        HIPCHK(h, hipGetLastError());
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(H, d + o_H, (size_t)nbins * 8, hipMemcpyDeviceToHost));
+    if (elev_out && n > 0) HIPCHK(h, hipMemcpy(elev_out, d + o_e, (size_t)n * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int lpc_elev_digit_pass(lpc_handle *h, int64_t n, const float *pos4, const float *pwr, const double *pole,
+                        uint64_t prefix, int shift, int bits, double *bin_pow, int64_t *bin_cnt,
+                        uint64_t *bin_maxkey)
+{
+    if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
+    RETIF(settle(h));
+    if (bits < 1 || bits > 12 || shift < 0 || shift + bits > 64 || !bin_pow || !bin_cnt || !bin_maxkey)
+        return set_err(h, LPC_E_ARG, "elev_digit_pass: bad argument (1 <= bits <= 12, 0 <= shift, shift + bits <= 64)");
+    ElevIn in;
+    char *d = nullptr;
+    const size_t nb = (size_t)1 << bits;
+    RETIF(elev_begin(h, "elev_digit_pass", n, pos4, pwr, pole, nb * 24, in, &d));
+    HIPCHK(h, hipMemsetAsync(d, 0, nb * 24, h->stream));
+    ElevDigitArgs A;
+    A.in = in;
+    A.all = shift + bits == 64;
+    A.prefix = A.all ? 0ull : (unsigned long long)prefix;
+    A.shift = shift;
+    A.bits = bits;
+    A.bin_pow = (double *)d;
+    A.bin_cnt = (unsigned long long *)(d + nb * 8);
+    A.bin_maxkey = (unsigned long long *)(d + nb * 16);
+    if (n > 0) {
+        if (bits <= 11)
+            hipLaunchKernelGGL(k_elev_digit<2048>, dim3(elev_grid(h, n, 4)), dim3(256), 0, h->stream, A);
+        else
+            hipLaunchKernelGGL(k_elev_digit<4096>, dim3(elev_grid(h, n, 2)), dim3(256), 0, h->stream, A);
+        HIPCHK(h, hipGetLastError());
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(bin_pow, d, nb * 8, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(bin_cnt, d + nb * 8, nb * 8, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(bin_maxkey, d + nb * 16, nb * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int lpc_elev_power_below(lpc_handle *h, int64_t n, const float *pos4, const float *pwr, const double *pole,
+                         double thr, int inclusive, double *power, int64_t *count, double *e_max)
+{
+    if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
+    RETIF(settle(h));
+    ElevIn in;
+    char *d = nullptr;
+    RETIF(elev_begin(h, "elev_power_below", n, pos4, pwr, pole, sizeof(ElevBelowOut), in, &d));
+    HIPCHK(h, hipMemsetAsync(d, 0, sizeof(ElevBelowOut), h->stream));
+    ElevBelowArgs A;
+    A.in = in;
+    A.thr = thr;
+    A.inclusive = inclusive != 0;
+    A.out = (ElevBelowOut *)d;
+    if (n > 0) {
+        hipLaunchKernelGGL(k_elev_below, dim3(elev_grid(h, n, 8)), dim3(256), 0, h->stream, A);
+        HIPCHK(h, hipGetLastError());
+    }
+    ElevBelowOut r;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(&r, d, sizeof(r), hipMemcpyDeviceToHost));
+    if (power) *power = r.power;
+    if (count) *count = (int64_t)r.count;
+    if (e_max) *e_max = r.count ? bits_to_double(r.emax_bits) : NAN;
+    return 0;
+}
+
 int lpc_filter_eval(lpc_handle *h, int64_t n, const float *origin3, const float *dir3, const float *rec5,
                     int mode, float *out_d)
 {

@@ -467,6 +467,76 @@ class Engine:
                                         ptr(y), ptr(pc)))
         return (H, xe, ye) if not want_xy else (H, xe, ye, x, y, pc)
 
+    # -- elevation passes (beam analysis) ---------------------------------------
+    @staticmethod
+    def _elev_points(pos4, pwr, pole):
+        """(n, pos4, pwr, pole) as the lpc_elev_* calls take them; pos4=None: the
+        device-resident measured record."""
+        pole = np.ascontiguousarray(np.asarray(pole, np.float64).reshape(-1))
+        if pole.size != 4:
+            raise ValueError("pole must have 4 components, as the (n,4) position rows")
+        if pos4 is None:
+            return 0, None, None, pole
+        p4 = f32(pos4, (-1, 4))
+        pw = f32(pwr).reshape(-1)
+        if pw.size != p4.shape[0]:
+            raise ValueError("one power per point")
+        return p4.shape[0], p4, pw, pole
+
+    def elev_scan(self, pole, pos4=None, pwr=None):
+        """Counts, elevation range and total power of the points (beam.Summary)."""
+        from .beam import Summary
+        n, p4, pw, pole = self._elev_points(pos4, pwr, pole)
+        s = _lib.ElevSummary()
+        self._c(self.L.lpc_elev_scan(self.h, n, ptr(p4), ptr(pw), ptr(pole), ctypes.byref(s)))
+        return Summary(s.n_valid, s.n_invalid, s.n_negative, s.e_min, s.e_max, s.total_power)
+
+    def elev_hist(self, points, pole, range=None, want_elev=False, pos4=None, pwr=None):
+        """np.histogram(elevation, bins=points, range=range, weights=float64(pwr)) on
+        the GPU -> (H, edges[, elevation]).  range=None scans the elevations first
+        and takes numpy's own range rule: (min, max), widened by 0.5 each way when
+        they are equal, (0, 1) without points; a non-finite elevation raises
+        ValueError, as np.histogram does for a non-finite range."""
+        if range is None:
+            s = self.elev_scan(pole, pos4, pwr)
+            if s.n_invalid > 0:
+                raise ValueError("elev_hist: %d points have no finite elevation (zero position or "
+                                 "non-unit pole)" % s.n_invalid)
+            lo, hi = (s.e_min, s.e_max) if s.n_valid > 0 else (0.0, 1.0)
+        else:
+            lo, hi = float(range[0]), float(range[1])
+        if lo == hi:
+            lo, hi = lo - 0.5, hi + 0.5
+        edges = np.ascontiguousarray(np.histogram(np.zeros(0), bins=points, range=(lo, hi))[1], np.float64)
+        n, p4, pw, pole = self._elev_points(pos4, pwr, pole)
+        nb = edges.size - 1
+        H = np.zeros(nb, np.float64)
+        elev = None
+        if want_elev:
+            elev = np.zeros(n if p4 is not None else self.measured()[0], np.float64)
+        self._c(self.L.lpc_elev_hist(self.h, n, ptr(p4), ptr(pw), ptr(pole), ptr(edges), nb, ptr(H), ptr(elev)))
+        return (H, edges, elev) if want_elev else (H, edges)
+
+    def elev_digit_pass(self, pole, prefix, shift, bits, pos4=None, pwr=None):
+        """One radix pass over the elevation keys -> (bin_pow, bin_cnt, bin_maxkey)."""
+        n, p4, pw, pole = self._elev_points(pos4, pwr, pole)
+        if not 1 <= bits <= 12:
+            raise ValueError("1 <= bits <= 12")
+        nb = 1 << bits
+        bp, bc, bk = np.zeros(nb, np.float64), np.zeros(nb, np.int64), np.zeros(nb, np.uint64)
+        self._c(self.L.lpc_elev_digit_pass(self.h, n, ptr(p4), ptr(pw), ptr(pole), int(prefix), int(shift),
+                                           int(bits), ptr(bp), ptr(bc), ptr(bk)))
+        return bp, bc, bk
+
+    def elev_power_below(self, pole, thr, inclusive=False, pos4=None, pwr=None):
+        """(power, count, largest elevation) of the points with e < thr (<= if inclusive)."""
+        n, p4, pw, pole = self._elev_points(pos4, pwr, pole)
+        p, c, e = ctypes.c_double(0.0), ctypes.c_int64(0), ctypes.c_double(0.0)
+        self._c(self.L.lpc_elev_power_below(self.h, n, ptr(p4), ptr(pw), ptr(pole), float(thr),
+                                            1 if inclusive else 0, ctypes.byref(p), ctypes.byref(c),
+                                            ctypes.byref(e)))
+        return p.value, c.value, e.value
+
     # -- profiling -------------------------------------------------------------
     def prof_enable(self, on=True, counters=False, light=False, every=1):
         """light: HIP events on the walk kernel's launches only, on every

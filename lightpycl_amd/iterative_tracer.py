@@ -22,6 +22,11 @@ set, so order-dependent reductions over them (a float32 ``np.sum``, the stable
 sort behind ``get_beam_width_half_power``'s tie-breaking) can differ from the
 reference in the last bits.  ``keep_results=True`` (the default) keeps the
 reference's order (iteration, then ray).
+
+Extra keyword ``on_device=True`` of ``get_beam_width_half_power``,
+``get_beam_HWHM`` and ``plot_elevation_histogram`` computes the elevation analyses
+with GPU passes over the measured record instead of fetching it (DESIGN.md
+section 9); the default is the reference's host code.
 """
 from __future__ import annotations
 
@@ -372,7 +377,48 @@ class CL_Tracer:
             plt.colorbar()
         plt.savefig(f"./{tag}_{'3D' if use_3d else '2D'}_data.pdf")
 
-    def plot_elevation_histogram(self, points=500, pole=[0, 0, 1, 0]):
+    # -- elevation analyses on the device (on_device=True) --------------------------
+    def _elev_device(self, pole):
+        """The elevation passes of this trace's measured rays on the GPU: the
+        device-resident record of an aggregate-mode trace, the measured rays as host
+        points otherwise.  -> (scan summary, keyword arguments naming the points), or
+        None when some power is negative or NaN (the caller takes the host path:
+        the device analyses assume a monotone cumulative power).  Non-finite
+        elevations raise ValueError, as np.histogram does for a non-finite range."""
+        if self._aggregate:
+            src = {}
+        else:
+            pos, pwr = self.get_measured_rays()
+            if pos is None:
+                pos, pwr = np.zeros((0, 4), np.float32), np.zeros(0, np.float32)
+            src = dict(pos4=pos, pwr=np.asarray(pwr).reshape(-1))
+        s = self.engine.elev_scan(pole, **src)
+        if s.n_invalid > 0:
+            raise ValueError("%d measured rays have no finite elevation against pole %r (zero position or "
+                             "non-unit pole)" % (s.n_invalid, list(pole)))
+        if s.n_negative > 0:
+            return None
+        return s, src
+
+    def _elev_hist_device(self, points, pole, s, src):
+        """np.histogram(elevation, bins=points, weights=float64(pwr)) from the device:
+        (H, bin centres)."""
+        rng = (s.e_min, s.e_max) if s.n_valid > 0 else (0.0, 1.0)
+        H, x = self.engine.elev_hist(points, pole, range=rng, **src)
+        return H, (x[0:-1] + x[1:]) / 2.0
+
+    def plot_elevation_histogram(self, points=500, pole=[0, 0, 1, 0], on_device=False):
+        """Elevation histogram of the measured power (:413-441).  ``on_device=True``
+        bins on the GPU (``lpc_elev_hist``) instead of fetching the measured rays."""
+        dev = self._elev_device(pole) if on_device else None
+        if dev is not None:
+            H, x = self._elev_hist_device(points, pole, *dev)
+            dx = x[1] - x[0]
+            H = H / (np.sin(x) * dx)
+            import matplotlib.pyplot as plt  # optional dependency
+            plt.plot(x * 180.0 / np.pi, H)
+            plt.savefig("./elevation_power_distribution.pdf")
+            return H, x
         (pos, pwr) = self.get_measured_rays()
         pos0 = np.array(np.divide(pos, np.matrix(np.linalg.norm(pos, axis=1)).T))
         pwr = np.float64(pwr).flatten()
@@ -386,8 +432,19 @@ class CL_Tracer:
         plt.savefig("./elevation_power_distribution.pdf")
         return H, x
 
-    def get_beam_width_half_power(self, points=500, pole=[0, 0, 1, 0]):
-        """Elevation at which the cumulative measured power reaches half (:443-466)."""
+    def get_beam_width_half_power(self, points=500, pole=[0, 0, 1, 0], on_device=False):
+        """Elevation at which the cumulative measured power reaches half (:443-466).
+        ``on_device=True`` selects it with a radix descent over GPU passes
+        (``beam.half_power``); rays of equal elevation then count as one group."""
+        dev = self._elev_device(pole) if on_device else None
+        if dev is not None:
+            from . import beam
+            s, src = dev
+            eng = self.engine
+            r = beam.half_power(lambda: s,
+                                lambda prefix, shift, bits: eng.elev_digit_pass(pole, prefix, shift, bits, **src),
+                                lambda thr, inclusive: eng.elev_power_below(pole, thr, inclusive, **src))
+            return r.total, np.array([r.elevation]) / np.pi * 180.0, np.array([r.cum_power]) / r.total * 100.0
         (pos, pwr0) = self.get_measured_rays()
         pos0 = np.array(np.divide(pos, np.matrix(np.linalg.norm(pos, axis=1)).T))
         pwr0 = np.float64(pwr0).reshape(-1)
@@ -399,8 +456,22 @@ class CL_Tracer:
         idx = np.where(np.absolute(cums - half) == min(np.absolute(cums - half)))
         return cums[-1], elevation[idx] / np.pi * 180.0, cums[idx] / cums[-1] * 100.0
 
-    def get_beam_HWHM(self, points=500, pole=[0, 0, 1, 0]):
-        """Half-width at half-maximum of the elevation intensity (:468-501)."""
+    def get_beam_HWHM(self, points=500, pole=[0, 0, 1, 0], on_device=False):
+        """Half-width at half-maximum of the elevation intensity (:468-501).
+        ``on_device=True``: the histogram and the power within the half-maximum
+        elevation come from GPU passes, the ``points``-bin part runs on the host."""
+        dev = self._elev_device(pole) if on_device else None
+        if dev is not None:
+            s, src = dev
+            H, x = self._elev_hist_device(points, pole, s, src)
+            H = (H.T / np.sin(x)).flatten()
+            hmax = max(H) / 2.0
+            idx = np.where(np.absolute(H - hmax) == min(np.absolute(H - hmax)))[0]
+            el = x[idx]
+            if el.size != 1:                  # the host path's `elevation0 < el` cannot broadcast either
+                raise ValueError("get_beam_HWHM: %d bins tie for the half maximum" % el.size)
+            within = self.engine.elev_power_below(pole, el[0], False, **src)[0]
+            return s.total_power, el / np.pi * 180.0, within / s.total_power * 100.0
         (pos, pwr0) = self.get_measured_rays()
         pos0 = np.array(np.divide(pos, np.matrix(np.linalg.norm(pos, axis=1)).T))
         pwr0 = np.float64(pwr0).reshape(-1)
