@@ -3,8 +3,29 @@ cumulative sum, and a numpy stand-in for the three device passes.  Not test
 cases themselves; tests/test_beam_host.py checks half_power_sorted against an
 independent plain-Python restatement."""
 import numpy as np
+import pytest
 
 from lightpycl_amd.beam import KEY_BITS, HalfPower, NonMonotonePower, Summary, key_of
+
+
+# Tolerances of the float64 beam outputs (derivation: tests/test_gpu_beam.py's docstring)
+ULP_PI = float(np.spacing(np.pi))
+ELEV_MEASURED = 4.44e-16                       # max |elev_out - host elevation|, traced cases (DESIGN.md 9)
+ELEV_TOL = max(8 * ELEV_MEASURED, 4 * ULP_PI)
+SUM_RTOL = 1e-12                               # float64 sums in atomic order (as test_gpu_postproc.py)
+
+
+@pytest.fixture()
+def no_pdf(monkeypatch, tmp_path):
+    """plot_elevation_histogram draws and saves a PDF: keep the drawing, skip the file.
+    (Test modules import this fixture by name.)"""
+    import matplotlib
+    matplotlib.use("Agg")
+    import matplotlib.pyplot as plt
+    monkeypatch.chdir(tmp_path)
+    monkeypatch.setattr(plt, "savefig", lambda *a, **k: None)
+    yield
+    plt.close("all")
 
 
 def half_power_sorted(elevation, power):

@@ -12,6 +12,9 @@ Each fixture holds the inputs (so a test can run from the fixture alone), the
 first-bounce outputs, the trace's per-iteration ray counts and the per-mesh
 measured power, plus the stock build's counts and power (`stock_*`: the same
 source built with OpenCL's default fp options, what PyOpenCL would run).
+
+The fixtures of the reference's Python layer (tests/golden/ref_host/*.npz) are
+not made here: `python oracle/ref_host.py` regenerates them where the reference is.
 """
 import os
 import sys

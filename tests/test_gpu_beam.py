@@ -7,19 +7,16 @@ poles used here (tests/test_beam_host.py); the elevation is acos of it, ocml's o
 the device and numpy's on the host.  The largest |device - host| elevation
 measured over the traced cases below was 4.44e-16 (one ulp(pi)); the bound is
 8 times that (the margin allows for another CPU's vectorised arccos), far below
-the margins the tests assert on their inputs (>= 1e6 ulp(pi))."""
+the margins the tests assert on their inputs (>= 1e6 ulp(pi)).  ELEV_TOL and
+SUM_RTOL live in tests/beam_ref.py, which tests/test_ref_host.py shares."""
 import beam_ref
 import numpy as np
 import pytest
+from beam_ref import ELEV_TOL, SUM_RTOL, ULP_PI, no_pdf  # noqa: F401  (no_pdf: a fixture)
 
 from lightpycl_amd import beam, scenes
 
 pytestmark = pytest.mark.gpu
-
-ULP_PI = float(np.spacing(np.pi))
-ELEV_MEASURED = 4.44e-16                       # max |elev_out - host elevation|, traced cases (DESIGN.md 9)
-ELEV_TOL = max(8 * ELEV_MEASURED, 4 * ULP_PI)
-SUM_RTOL = 1e-12                               # float64 sums in atomic order (as test_gpu_postproc.py)
 
 POLE_Z, POLE_X, POLE_NY = [0, 0, 1, 0], [1, 0, 0, 0], [0, -1, 0, 0]
 
@@ -165,18 +162,6 @@ def traced():
     return out
 
 
-@pytest.fixture()
-def no_pdf(monkeypatch, tmp_path):
-    """plot_elevation_histogram draws and saves a PDF: keep the drawing, skip the file."""
-    import matplotlib
-    matplotlib.use("Agg")
-    import matplotlib.pyplot as plt
-    monkeypatch.chdir(tmp_path)
-    monkeypatch.setattr(plt, "savefig", lambda *a, **k: None)
-    yield
-    plt.close("all")
-
-
 @pytest.mark.parametrize("npts", [90, 500])
 @pytest.mark.parametrize("pole", [POLE_Z, POLE_X])
 @pytest.mark.parametrize("keep", [True, False])
@@ -246,3 +231,167 @@ def test_default_keyword_is_the_host_path(traced, monkeypatch):
     tr.get_beam_width_half_power()
     tr.get_beam_HWHM(points=90)
     tr.get_beam_HWHM(points=90, on_device=False)
+
+
+# -- past one grid of rows: the grid-stride step of the four elevation kernels ------------
+def _cus(engine):
+    """The CU count that caps the kernels' grids (elev_grid: h->cus, read from
+    hipDeviceProp_t::multiProcessorCount, the property torch reports)."""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert engine.info()[1] == cus
+    return cus
+
+
+@pytest.fixture(scope="module")
+def big(engine):
+    """n = 8 cus 256 + 64 cus + 257 points: the scan, histogram and below kernels
+    (8 blocks per CU) take 2 trips, the 11-bit digit kernel (4) 3, the 12-bit one
+    (2) 5; the last trip is partly filled (n is odd: the last block is ragged) and
+    most blocks have none.  Repeated elevations, zero powers, three zero rows
+    (no elevation) beyond the first trip.  -> points, the host elevations and the
+    device's own (elev_out)."""
+    cus = _cus(engine)
+    first = 8 * cus * 256
+    n = first + 64 * cus + 257
+    pos, pw = points(n, seed=5)
+    pos[5::7] = pos[3]
+    pw[::11] = 0.0
+    zero = np.array([first + 1, first + 32 * cus + 5, n - 2])
+    pos[zero] = 0.0
+    e = host_elevation(pos, POLE_Z)
+    ok = np.isfinite(e)
+    assert (~ok).sum() == 3 and not ok[zero].any()
+    _, _, ed = engine.elev_hist(90, POLE_Z, range=(0.0, np.pi), want_elev=True, pos4=pos, pwr=pw)
+    return dict(cus=cus, first=first, n=n, pos=pos, pw=pw, e=e, ok=ok, ed=ed, src=dict(pos4=pos, pwr=pw))
+
+
+def test_big_scan_and_elev_out(engine, big):
+    e, ok, ed, pw = big["e"], big["ok"], big["ed"], big["pw"]
+    assert ed.shape == (big["n"],)
+    assert np.array_equal(np.isnan(ed), ~ok)                       # every row written, the last trip's too
+    err = np.abs(ed[ok] - e[ok])
+    print("max |elev_out - host| %.3g, beyond the first trip %.3g" % (err.max(), err[big["first"] - 3:].max()))
+    assert err.max() <= ELEV_TOL
+    s = engine.elev_scan(POLE_Z, **big["src"])
+    assert (s.n_valid, s.n_invalid, s.n_negative) == (big["n"] - 3, 3, 0)
+    assert abs(s.e_min - e[ok].min()) <= ELEV_TOL and abs(s.e_max - e[ok].max()) <= ELEV_TOL
+    assert s.e_min == ed[ok].min() and s.e_max == ed[ok].max()
+    np.testing.assert_allclose(s.total_power, pw[ok].astype(np.float64).sum(), rtol=SUM_RTOL)
+
+
+def _check_digit_pass(engine, big, P, prefix, shift, bits):
+    bp, bc, bk = engine.elev_digit_pass(POLE_Z, prefix, shift, bits, **big["src"])
+    wp, wc, wk = P.digit_pass(prefix, shift, bits)
+    assert bc.shape == (1 << bits,) and wc.sum() > 0
+    np.testing.assert_array_equal(bc, wc)
+    np.testing.assert_array_equal(bk, wk)                           # each bin's largest key, of elev_out
+    np.testing.assert_allclose(bp, wp, rtol=SUM_RTOL)
+    return bc
+
+
+def test_big_digit_passes(engine, big):
+    P = beam_ref.NumpyPasses(big["ed"], big["pw"])
+    bc = _check_digit_pass(engine, big, P, 0, 52, 12)
+    assert bc.sum() == big["n"] - 3
+    top = int(np.argmax(bc))                                        # a populated prefix, one level down
+    assert bc[top] > 4096
+    c12 = _check_digit_pass(engine, big, P, top, 40, 12)
+    c11 = _check_digit_pass(engine, big, P, top, 41, 11)
+    assert c12.sum() == c11.sum() == bc[top]
+    _check_digit_pass(engine, big, P, 0, 53, 11)                    # the 11-bit kernel over every row
+
+
+@pytest.mark.parametrize("bins", [90, 5000])
+def test_big_hist(engine, big, bins):
+    """The LDS kernel (90 bins) and the global-atomics one (5000) against
+    np.histogram of the device's own elevations."""
+    ok, ed = big["ok"], big["ed"]
+    w = big["pw"].astype(np.float64)
+    lo, hi = float(ed[ok].min()), float(ed[ok].max())
+    H, edges, ed2 = engine.elev_hist(bins, POLE_Z, range=(lo, hi), want_elev=True, **big["src"])
+    np.testing.assert_array_equal(ed2, ed)                          # NaN rows equal as NaN
+    Hn, en = np.histogram(ed[ok], bins=bins, range=(lo, hi), weights=w[ok])
+    np.testing.assert_array_equal(edges, en)
+    np.testing.assert_allclose(H, Hn, rtol=SUM_RTOL, atol=SUM_RTOL * Hn.max())
+    H2, _ = engine.elev_hist(bins, POLE_Z, range=(0.5, 2.0), **big["src"])
+    Hn2, _ = np.histogram(ed[ok], bins=bins, range=(0.5, 2.0), weights=w[ok])
+    np.testing.assert_allclose(H2, Hn2, rtol=SUM_RTOL, atol=SUM_RTOL * Hn2.max())
+
+
+def test_big_power_below_and_half_power(engine, big):
+    ok, ed, pw, src = big["ok"], big["ed"], big["pw"], big["src"]
+    thr = float(ed[3])                                              # a repeated elevation
+    assert (ed == thr).sum() > big["n"] // 8
+    for incl in (False, True):
+        sel = ok & ((ed <= thr) if incl else (ed < thr))
+        p, c, em = engine.elev_power_below(POLE_Z, thr, incl, **src)
+        assert c == sel.sum() and em == ed[sel].max()
+        np.testing.assert_allclose(p, pw[sel].astype(np.float64).sum(), rtol=SUM_RTOL)
+    want = beam_ref.half_power_sorted(ed, pw)
+    for bits in (11, 12):
+        got = beam.half_power(lambda: engine.elev_scan(POLE_Z, **src),
+                              lambda pf, sh, b: engine.elev_digit_pass(POLE_Z, pf, sh, b, **src),
+                              lambda t, i: engine.elev_power_below(POLE_Z, t, i, **src), bits=bits)
+        assert got.key == want.key and got.elevation == want.elevation
+        np.testing.assert_allclose([got.total, got.cum_power], [want.total, want.cum_power], rtol=SUM_RTOL)
+
+
+def test_big_device_record_vs_the_same_points_from_the_host(engine, no_pdf):
+    """The device-resident record (px / py / pz planes, aggregate mode only) past
+    one grid of rows: every pass and the three on_device analyses over it against
+    the same engine's passes over fetch_measured() handed back as host points.
+    Same elevations on both sides, so counts, ranges and selected keys are exact
+    and only the sums' order is free."""
+    from lightpycl_amd.iterative_tracer import CL_Tracer
+    first = 8 * _cus(engine) * 256
+    sc = scenes.lens(n=int(first / 1.75) + 1000, seed=9)            # ~1.92 measured rays per emitted ray
+    tr = CL_Tracer(device=0)
+    tr.iterative_tracer(sc.sources, sc.meshes, trace_iterations=sc.iterations, trace_until_dissipated=sc.tau,
+                        max_ray_len=sc.max_ray_len, ior_env=sc.ior_env, keep_results=False)
+    eng = tr.engine
+    pos, pw, _ = eng.fetch_measured()
+    print("measured rays", pos.shape[0], "first trip", first)
+    assert pos.shape[0] > first + 256
+    src = dict(pos4=pos, pwr=pw)
+    dev = {}
+    for pole in (POLE_Z, POLE_X):
+        s0, s1 = eng.elev_scan(pole), eng.elev_scan(pole, **src)
+        assert s0[:5] == s1[:5] and s0.n_valid == pos.shape[0]
+        np.testing.assert_allclose(s0.total_power, s1.total_power, rtol=SUM_RTOL)
+        for prefix, shift, bits in ((0, 52, 12), (0, 53, 11)):
+            a, b = eng.elev_digit_pass(pole, prefix, shift, bits), eng.elev_digit_pass(pole, prefix, shift, bits, **src)
+            np.testing.assert_array_equal(a[1], b[1])
+            np.testing.assert_array_equal(a[2], b[2])
+            np.testing.assert_allclose(a[0], b[0], rtol=SUM_RTOL)
+        thr = (s0.e_min + s0.e_max) / 2.0
+        a, b = eng.elev_power_below(pole, thr, True), eng.elev_power_below(pole, thr, True, **src)
+        assert a[1:] == b[1:] and 0 < a[1] < pos.shape[0]
+        np.testing.assert_allclose(a[0], b[0], rtol=SUM_RTOL)
+        _, _, e0 = eng.elev_hist(90, pole, want_elev=True)
+        _, _, e1 = eng.elev_hist(90, pole, want_elev=True, **src)
+        np.testing.assert_array_equal(e0, e1)
+        for npts in (90, 5000):
+            dev[tuple(pole), npts] = (tr.plot_elevation_histogram(points=npts, pole=pole, on_device=True),
+                                      tr.get_beam_width_half_power(points=npts, pole=pole, on_device=True),
+                                      tr.get_beam_HWHM(points=npts, pole=pole, on_device=True))
+    assert tr._elev_device(POLE_Z)[1] == {}                         # so far: the device-resident record
+    # the same tracer over the fetched rays as host points (results mode's source of _elev_device)
+    tr._aggregate = False
+    tr.results = [(pos, pos, pw, np.ones(pos.shape[0], np.int32))]
+    src2 = tr._elev_device(POLE_Z)[1]                               # from here on: these host points
+    assert set(src2) == {"pos4", "pwr"} and src2["pos4"].shape == pos.shape
+    np.testing.assert_array_equal(src2["pos4"], pos)
+    np.testing.assert_array_equal(src2["pwr"], pw)
+    for (pole, npts), ((H0, x0), (t0, a0, c0), (u0, b0, w0)) in dev.items():
+        pole = list(pole)
+        H1, x1 = tr.plot_elevation_histogram(points=npts, pole=pole, on_device=True)
+        np.testing.assert_array_equal(x0, x1)
+        np.testing.assert_allclose(H0, H1, rtol=SUM_RTOL, atol=SUM_RTOL * np.abs(H1).max())
+        t1, a1, c1 = tr.get_beam_width_half_power(points=npts, pole=pole, on_device=True)
+        np.testing.assert_array_equal(a0, a1)
+        assert np.shape(a0) == np.shape(c0) == (1,)
+        np.testing.assert_allclose([t0, c0[0]], [t1, c1[0]], rtol=SUM_RTOL)
+        u1, b1, w1 = tr.get_beam_HWHM(points=npts, pole=pole, on_device=True)
+        np.testing.assert_array_equal(b0, b1)
+        np.testing.assert_allclose([u0, float(w0)], [u1, float(w1)], rtol=SUM_RTOL)
