@@ -326,6 +326,57 @@ int lpc_elev_digit_pass(lpc_handle *h, int64_t n, const float *pos4, const float
 int lpc_elev_power_below(lpc_handle *h, int64_t n, const float *pos4, const float *pwr, const double *pole,
                          double thr, int inclusive, double *power, int64_t *count, double *e_max);
 
+/* ---- light sources born on the device (light_source.py:98-188) ------------- */
+/* numpy's legacy generator (np.random.seed / np.random.rand: MT19937, a double
+ * from two tempered 32-bit outputs, (a 2^26 + b) / 2^53 with a = w0 >> 5,
+ * b = w1 >> 6) continued on the device.  key[624] and *pos (0..624) are a
+ * RandomState state (np.random.get_state()[1:3]); they are advanced in place
+ * over n doubles, which are written to host_out (double[n]) bit for bit as
+ * random_sample makes them, or only skipped when host_out is NULL. */
+int lpc_rng_mt19937(lpc_handle *h, uint32_t *key, int32_t *pos, int64_t n, double *host_out);
+/* A device-resident source: origin (n,4), direction (n,4) and power[n] in plain
+ * device memory on the emitting handle's device, plus the float64 sum of its
+ * powers.  Any handle of that device may rotate, fetch or trace it (its stream
+ * waits on an event of the stream that wrote the source last); a handle of
+ * another device refuses it with LPC_E_ARG. */
+typedef struct lpc_rays lpc_rays;
+/* random_rays (light_source.py:98-137) of an n-ray source: the stream's next n
+ * doubles are u, the n after them v; elevation acos(u), azimuth (2 pi) v, the
+ * direction row times Rx9 times Rz9 (row-major 3x3 float64, the upper-left of
+ * _Rx(elev0) / _Rz(az0)), float64 with no contraction, then cast to float32.
+ * Origins are center4 (float32[4]) rows.  Power: w = float32(cos(el) ** m),
+ * m >= 0 (1: the reference's default directivity, 0: isotropic), then
+ * w * float32(power) / float32(S) in float32, S the float64 sum of w over all n
+ * rays in a fixed tile order (the same bits on every run).  Only rays
+ * [first, first + count) are written to *out (a rank's shard); the generator
+ * advances over all 2 n draws and S covers all n.  LPC_E_ARG: n < 1, the shard
+ * outside [0, n], m < 0. */
+int lpc_rays_emit_hemisphere(lpc_handle *h, uint32_t *key, int32_t *pos, int64_t n, int64_t first, int64_t count,
+                             const float *center4, const double *Rx9, const double *Rz9, double power, double m,
+                             lpc_rays **out);
+/* random_collimated_rays (light_source.py:139-170): draws x then y (n each);
+ * origin ((x - 0.5) d, (y - 0.5) d, 0) . Rx9 . Rz9 cast to float32, plus center4
+ * in float32; direction the constant dir_row3 (float32[3], computed by the
+ * caller); equal powers float32(power) / float32(n) (bit-equal to the host's for
+ * n <= 2^24).  Shards as above. */
+int lpc_rays_emit_collimated(lpc_handle *h, uint32_t *key, int32_t *pos, int64_t n, int64_t first, int64_t count,
+                             double diameter, const float *center4, const double *Rx9, const double *Rz9,
+                             const float *dir_row3, double power, lpc_rays **out);
+/* rotate_rays (light_source.py:173-188): origin = (origin - pivot) . R9 + pivot,
+ * dir = dir . R9 in float64, cast to float32 (pivot4: double[4]; the origin's w
+ * becomes pivot4[3]).  Queued on h's stream. */
+int lpc_rays_rotate(lpc_handle *h, lpc_rays *r, const double *R9, const double *pivot4);
+/* Ray count and float64 power sum of r (either output may be NULL). */
+int lpc_rays_info(const lpc_rays *r, int64_t *n, double *power_sum);
+/* Copy r to host arrays (any may be NULL): origin4 (n,4), dir4 (n,4), pow[n]. */
+int lpc_rays_fetch(lpc_handle *h, const lpc_rays *r, float *origin4, float *dir4, float *pow);
+int lpc_rays_free(lpc_rays *r);
+/* lpc_trace_set_rays from device sources: the `count` sources of `list`
+ * concatenated in list order, device to device, become the emitted rays (the
+ * same analysis, and the copy lpc_trace_reset restores).  The sources are only
+ * read and may be freed or traced again afterwards. */
+int lpc_trace_set_rays_dev(lpc_handle *h, lpc_rays *const *list, int32_t count, float max_ray_len, float ior_env);
+
 /* ---- diagnostics ---------------------------------------------------------- */
 /* The device's own conservative-filter code on n (ray, record) pairs, host
  * arrays: origin3/dir3 (n,3), rec5 (n,5) = centre xyz, negB, negA (filter_record /

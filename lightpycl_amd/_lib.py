@@ -105,6 +105,14 @@ _PROTOS = {
     "lpc_shm_allreduce": [_P, _P, _I32],
     "lpc_shm_comm_abort": [_P],
     "lpc_shm_comm_close": [_P],
+    "lpc_rng_mt19937": [_P, _P, _P, _I64, _P],
+    "lpc_rays_emit_hemisphere": [_P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _F64, _F64, _P],
+    "lpc_rays_emit_collimated": [_P, _P, _P, _I64, _I64, _I64, _F64, _P, _P, _P, _P, _F64, _P],
+    "lpc_rays_rotate": [_P, _P, _P, _P],
+    "lpc_rays_info": [_P, _P, _P],
+    "lpc_rays_fetch": [_P, _P, _P, _P, _P],
+    "lpc_rays_free": [_P],
+    "lpc_trace_set_rays_dev": [_P, _P, _I32, _F32, _F32],
 }
 
 # lpc_allreduce_fn (include/lpc.h): int (*)(void *ctx, double *vals, int32_t n)

@@ -4,6 +4,7 @@
 // vertex records + mesh tables), a chunk workspace and the device-resident ray
 // population of a trace.  All launches go to the handle's stream.
 #include "lpc_kernels.hip"
+#include "lpc_emit.hip"
 #include "lpc.h"
 #include "lpc_comm.hpp"
 #include "lpc_build.hpp"
@@ -249,6 +250,8 @@ struct lpc_handle {
     DBuf d_scan;                                    // RayScan of set_rays (k_ray_scan)
     DBuf d_stats;                                   // walk counters (profiling)
     DBuf d_fan;                                     // profiling: fan-triangle flags (SpillArgs::fan)
+    DBuf d_mt, d_rng, d_etile;                      // device-born sources: generator state (key | pos), its
+                                                    //   doubles, the fixed-order sums' tiles
     // profiling
     bool prof = false, prof_stats = false, prof_light = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_isect, ev_rest, ev_kern;
@@ -1413,7 +1416,8 @@ int lpc_close(lpc_handle *h)
                     &h->w_shf, &h->w_shi, &h->w_blk_cnt, &h->w_blk_off, &h->w_blk_pow, &h->w_soa,
                     &h->w_stage, &h->w_sort, &h->w_sort_tmp, &h->w_bhist, &h->d_srec, &h->A.buf, &h->B.buf, &h->T.buf, &h->I.buf, &h->m_buf,
                     &h->d_acc, &h->d_tmp, &h->d_scan, &h->d_stats, &h->d_misc, &h->w_spill, &h->w_qroots,
-                    &h->w_aos, &h->w_fc, &h->d_mrun, &h->w_gsum, &h->d_ctl, &h->d_cbase, &h->w_tbox, &h->d_pbox};
+                    &h->w_aos, &h->w_fc, &h->d_mrun, &h->w_gsum, &h->d_ctl, &h->d_cbase, &h->w_tbox, &h->d_pbox,
+                    &h->d_mt, &h->d_rng, &h->d_etile};
     for (DBuf *b : bufs) dfree(*b);
     if (h->acc_host) (void)hipHostFree(h->acc_host);
     h->acc_host = nullptr;
@@ -3359,6 +3363,291 @@ int lpc_prof_read(lpc_handle *h, lpc_prof *out, int reset)
         if (h->d_stats.p) HIPCHK(h, hipMemset(h->d_stats.p, 0, LPC_STATS_WORDS * 8));
     }
     return 0;
+}
+
+// ---- light sources born on the device (light_source.py:98-188) ---------------
+// The generator's state travels through d_mt (key[624] | pos), its doubles stay
+// in d_rng; both kernels queue on the handle's stream.  mt_collect waits for them
+// and reads the advanced state back.
+static int mt_enqueue(lpc_handle *h, const char *who, const uint32_t *key, const int32_t *pos, int64_t n, bool fill)
+{
+    if (!key || !pos) return set_err(h, LPC_E_ARG, std::string(who) + ": key or pos is NULL");
+    if (*pos < 0 || *pos > LPC_MT_N) return set_err(h, LPC_E_ARG, std::string(who) + ": pos outside 0..624");
+    if (n < 0 || n > ((int64_t)1 << 60)) return set_err(h, LPC_E_ARG, std::string(who) + ": bad draw count");
+    HIPCHK(h, hipSetDevice(h->device));
+    RETIF(dalloc(h, h->d_mt, (LPC_MT_N + 1) * 4));
+    if (fill) RETIF(dalloc(h, h->d_rng, (size_t)n * 8));
+    uint32_t st[LPC_MT_N + 1];
+    memcpy(st, key, LPC_MT_N * 4);
+    st[LPC_MT_N] = (uint32_t)*pos;
+    HIPCHK(h, hipStreamSynchronize(h->stream));      // d_mt may still be read by an earlier call's kernel
+    HIPCHK(h, hipMemcpy(h->d_mt.p, st, sizeof(st), hipMemcpyHostToDevice));
+    if (n > 0) {
+        hipLaunchKernelGGL(k_mt19937, dim3(1), dim3(LPC_MT_THREADS), 0, h->stream, (uint32_t *)h->d_mt.p,
+                           (int32_t *)h->d_mt.p + LPC_MT_N, n, fill ? (double *)h->d_rng.p : (double *)nullptr);
+        HIPCHK(h, hipGetLastError());
+    }
+    return 0;
+}
+
+static int mt_collect(lpc_handle *h, uint32_t *key, int32_t *pos)
+{
+    uint32_t st[LPC_MT_N + 1];
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(st, h->d_mt.p, sizeof(st), hipMemcpyDeviceToHost));
+    memcpy(key, st, LPC_MT_N * 4);
+    *pos = (int32_t)st[LPC_MT_N];
+    return 0;
+}
+
+int lpc_rng_mt19937(lpc_handle *h, uint32_t *key, int32_t *pos, int64_t n, double *host_out)
+{
+    if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
+    RETIF(mt_enqueue(h, "rng_mt19937", key, pos, n, host_out != nullptr));
+    RETIF(mt_collect(h, key, pos));
+    if (host_out && n > 0) HIPCHK(h, hipMemcpy(host_out, h->d_rng.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+}  // extern "C"
+
+// A device-resident source: (n,4) origin and direction rows and power[n] in plain
+// device memory, the float64 sum of its powers, and an event the last kernel that
+// wrote it recorded (a consumer on another stream waits on it).
+struct lpc_rays {
+    int device = 0;
+    float4 *origin = nullptr, *dir = nullptr;
+    float *pow = nullptr;
+    int64_t n = 0;
+    double power_sum = 0.0;
+    hipEvent_t ready = nullptr;
+};
+
+static void rays_destroy(lpc_rays *r)
+{
+    if (!r) return;
+    if (r->ready) { (void)hipEventSynchronize(r->ready); (void)hipEventDestroy(r->ready); }
+    if (r->origin) (void)hipFree(r->origin);
+    if (r->dir) (void)hipFree(r->dir);
+    if (r->pow) (void)hipFree(r->pow);
+    delete r;
+}
+
+static int rays_create(lpc_handle *h, int64_t n, lpc_rays **out)
+{
+    lpc_rays *r = new lpc_rays();
+    r->device = h->device;
+    r->n = n;
+    const size_t rows = (size_t)std::max<int64_t>(n, 1);
+    hipError_t e = hipMalloc((void **)&r->origin, rows * 16);
+    if (e == hipSuccess) e = hipMalloc((void **)&r->dir, rows * 16);
+    if (e == hipSuccess) e = hipMalloc((void **)&r->pow, rows * 4);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&r->ready, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        rays_destroy(r);
+        return set_err(h, LPC_E_NOMEM, std::string("device source of ") + std::to_string(n) + " rays: " +
+                                           hipGetErrorString(e));
+    }
+    *out = r;
+    return 0;
+}
+
+static int emit_check(lpc_handle *h, const char *who, int64_t n, int64_t first, int64_t count, const float *center4,
+                      const double *Rx9, const double *Rz9, lpc_rays **out)
+{
+    if (!center4 || !Rx9 || !Rz9 || !out) return set_err(h, LPC_E_ARG, std::string(who) + ": null argument");
+    if (n < 1) return set_err(h, LPC_E_ARG, std::string(who) + ": n < 1");
+    if (first < 0 || count < 0 || first > n || count > n - first)
+        return set_err(h, LPC_E_ARG, std::string(who) + ": shard [first, first + count) outside [0, n]");
+    return 0;
+}
+
+// hemisphere: the generator, the weights' sum, the shard's rays and their power
+// sum, all queued on the stream; one wait at the end
+static int emit_hemisphere(lpc_handle *h, lpc_rays *r, uint32_t *key, int32_t *pos, EmitArgs A)
+{
+    RETIF(mt_enqueue(h, "emit_hemisphere", key, pos, 2 * A.n, true));
+    const int64_t nt = (A.n + LPC_EMIT_TILE - 1) / LPC_EMIT_TILE, nb = (A.count + 255) / 256;
+    RETIF(dalloc(h, h->d_etile, (size_t)(2 + nt + nb) * 8));
+    double *sums = (double *)h->d_etile.p, *wt = sums + 2, *pt = wt + nt;
+    A.draws = (const double *)h->d_rng.p;
+    A.wsum = sums;
+    A.tile = pt;
+    hipLaunchKernelGGL(k_emit_weights, dim3((unsigned)nt), dim3(256), 0, h->stream, A.draws, A.n, A.m, wt);
+    hipLaunchKernelGGL(k_sum_tiles, dim3(1), dim3(256), 0, h->stream, (const double *)wt, nt, sums);
+    if (nb > 0) hipLaunchKernelGGL(k_emit_hemisphere, dim3((unsigned)nb), dim3(256), 0, h->stream, A);
+    hipLaunchKernelGGL(k_sum_tiles, dim3(1), dim3(256), 0, h->stream, (const double *)pt, nb, sums + 1);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(r->ready, h->stream));
+    RETIF(mt_collect(h, key, pos));
+    HIPCHK(h, hipMemcpy(&r->power_sum, sums + 1, 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+static int emit_collimated(lpc_handle *h, lpc_rays *r, uint32_t *key, int32_t *pos, EmitArgs A)
+{
+    RETIF(mt_enqueue(h, "emit_collimated", key, pos, 2 * A.n, true));
+    A.draws = (const double *)h->d_rng.p;
+    const int64_t nb = (A.count + 255) / 256;
+    if (nb > 0) hipLaunchKernelGGL(k_emit_collimated, dim3((unsigned)nb), dim3(256), 0, h->stream, A);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(r->ready, h->stream));
+    RETIF(mt_collect(h, key, pos));
+    r->power_sum = (double)A.power * (double)A.count;
+    return 0;
+}
+
+extern "C" {
+
+int lpc_rays_emit_hemisphere(lpc_handle *h, uint32_t *key, int32_t *pos, int64_t n, int64_t first, int64_t count,
+                             const float *center4, const double *Rx9, const double *Rz9, double power, double m,
+                             lpc_rays **out)
+{
+    if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
+    RETIF(emit_check(h, "emit_hemisphere", n, first, count, center4, Rx9, Rz9, out));
+    if (!(m >= 0.0)) return set_err(h, LPC_E_ARG, "emit_hemisphere: directivity exponent m < 0");
+    *out = nullptr;
+    HIPCHK(h, hipSetDevice(h->device));
+    EmitArgs A;
+    memset(&A, 0, sizeof(A));
+    A.n = n; A.first = first; A.count = count;
+    memcpy(A.Rx, Rx9, sizeof(A.Rx));
+    memcpy(A.Rz, Rz9, sizeof(A.Rz));
+    memcpy(A.center, center4, sizeof(A.center));
+    A.power = (float)power;
+    A.m = m;
+    lpc_rays *r = nullptr;
+    RETIF(rays_create(h, count, &r));
+    A.origin = r->origin; A.dirs = r->dir; A.pow = r->pow;
+    const int rc = emit_hemisphere(h, r, key, pos, A);
+    if (rc) { rays_destroy(r); return rc; }
+    *out = r;
+    return 0;
+}
+
+int lpc_rays_emit_collimated(lpc_handle *h, uint32_t *key, int32_t *pos, int64_t n, int64_t first, int64_t count,
+                             double diameter, const float *center4, const double *Rx9, const double *Rz9,
+                             const float *dir_row3, double power, lpc_rays **out)
+{
+    if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
+    RETIF(emit_check(h, "emit_collimated", n, first, count, center4, Rx9, Rz9, out));
+    if (!dir_row3) return set_err(h, LPC_E_ARG, "emit_collimated: null argument");
+    *out = nullptr;
+    HIPCHK(h, hipSetDevice(h->device));
+    EmitArgs A;
+    memset(&A, 0, sizeof(A));
+    A.n = n; A.first = first; A.count = count;
+    memcpy(A.Rx, Rx9, sizeof(A.Rx));
+    memcpy(A.Rz, Rz9, sizeof(A.Rz));
+    memcpy(A.center, center4, sizeof(A.center));
+    memcpy(A.dir, dir_row3, sizeof(A.dir));
+    // equal powers: ones * float32(power) / float32(sum of n ones)
+    A.power = emit_power(1.0f, (float)power, (float)(double)n);
+    A.diameter = diameter;
+    lpc_rays *r = nullptr;
+    RETIF(rays_create(h, count, &r));
+    A.origin = r->origin; A.dirs = r->dir; A.pow = r->pow;
+    const int rc = emit_collimated(h, r, key, pos, A);
+    if (rc) { rays_destroy(r); return rc; }
+    *out = r;
+    return 0;
+}
+
+int lpc_rays_rotate(lpc_handle *h, lpc_rays *r, const double *R9, const double *pivot4)
+{
+    if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
+    if (!r || !R9 || !pivot4) return set_err(h, LPC_E_ARG, "rays_rotate: null argument");
+    if (r->device != h->device) return set_err(h, LPC_E_ARG, "rays_rotate: the source lives on another device");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (r->n > 0) {
+        RotateArgs A;
+        A.n = r->n;
+        memcpy(A.R, R9, sizeof(A.R));
+        memcpy(A.piv, pivot4, sizeof(A.piv));
+        A.origin = r->origin; A.dirs = r->dir;
+        HIPCHK(h, hipStreamWaitEvent(h->stream, r->ready, 0));
+        hipLaunchKernelGGL(k_rays_rotate, dim3(grid1(r->n)), dim3(256), 0, h->stream, A);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipEventRecord(r->ready, h->stream));
+    }
+    return 0;
+}
+
+int lpc_rays_info(const lpc_rays *r, int64_t *n, double *power_sum)
+{
+    if (!r) return set_err(nullptr, LPC_E_ARG, "rays_info: null source");
+    if (n) *n = r->n;
+    if (power_sum) *power_sum = r->power_sum;
+    return 0;
+}
+
+int lpc_rays_fetch(lpc_handle *h, const lpc_rays *r, float *origin4, float *dir4, float *pow)
+{
+    if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
+    if (!r) return set_err(h, LPC_E_ARG, "rays_fetch: null source");
+    HIPCHK(h, hipSetDevice(r->device));
+    HIPCHK(h, hipEventSynchronize(r->ready));
+    if (r->n > 0) {
+        if (origin4) HIPCHK(h, hipMemcpy(origin4, r->origin, (size_t)r->n * 16, hipMemcpyDeviceToHost));
+        if (dir4) HIPCHK(h, hipMemcpy(dir4, r->dir, (size_t)r->n * 16, hipMemcpyDeviceToHost));
+        if (pow) HIPCHK(h, hipMemcpy(pow, r->pow, (size_t)r->n * 4, hipMemcpyDeviceToHost));
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    return 0;
+}
+
+int lpc_rays_free(lpc_rays *r)
+{
+    if (!r) return 0;
+    (void)hipSetDevice(r->device);
+    rays_destroy(r);
+    return 0;
+}
+
+int lpc_trace_set_rays_dev(lpc_handle *h, lpc_rays *const *list, int32_t count, float max_ray_len, float ior_env)
+{
+    if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
+    RETIF(settle(h));                   // a trace still running (lpc_trace_iterate / _run_async)
+    if (!h->M) return set_err(h, LPC_E_STATE, "no scene uploaded");
+    if (count < 0 || (count > 0 && !list)) return set_err(h, LPC_E_ARG, "set_rays_dev: missing source list");
+    int64_t n = 0;
+    for (int32_t k = 0; k < count; ++k) {
+        if (!list[k]) return set_err(h, LPC_E_ARG, "set_rays_dev: null source");
+        if (list[k]->device != h->device)
+            return set_err(h, LPC_E_ARG, "set_rays_dev: a source lives on another device");
+        n += list[k]->n;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    RETIF(pop_reserve(h, h->I, std::max<int64_t>(n, 1)));
+    RayScan S;
+    memset(&S, 0, sizeof(S));
+    if (n > 0) {
+        // the sources in list order, device to device; each after its producer's
+        // last kernel (an event of the producing stream, no host wait)
+        int64_t off = 0;
+        for (int32_t k = 0; k < count; ++k) {
+            const lpc_rays *r = list[k];
+            if (r->n == 0) continue;
+            HIPCHK(h, hipStreamWaitEvent(h->stream, r->ready, 0));
+            hipLaunchKernelGGL(k_unpack4, dim3(grid1(r->n)), dim3(256), 0, h->stream, r->n, (const float4 *)r->origin,
+                               h->I.f(0) + off, h->I.f(1) + off, h->I.f(2) + off);
+            hipLaunchKernelGGL(k_unpack4, dim3(grid1(r->n)), dim3(256), 0, h->stream, r->n, (const float4 *)r->dir,
+                               h->I.f(3) + off, h->I.f(4) + off, h->I.f(5) + off);
+            HIPCHK(h, hipMemcpyAsync(h->I.f(6) + off, r->pow, (size_t)r->n * 4, hipMemcpyDeviceToDevice, h->stream));
+            off += r->n;
+        }
+        HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)h->I.pmid(), -2, (size_t)n, h->stream));
+        RETIF(dalloc(h, h->d_scan, sizeof(RayScan)));
+        HIPCHK(h, hipMemsetAsync(h->d_scan.p, 0, sizeof(RayScan), h->stream));
+        hipLaunchKernelGGL(k_ray_scan, dim3((unsigned)std::min<int64_t>(grid1(n), 2048)), dim3(256), 0, h->stream,
+                           h->I.in(), n, h->box_lo[0], h->box_lo[1], h->box_lo[2], h->box_scale[0], h->box_scale[1],
+                           h->box_scale[2], (RayScan *)h->d_scan.p);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(&S, h->d_scan.p, sizeof(RayScan), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return emitted_rays(h, n, S, max_ray_len, ior_env);
 }
 
 }  // extern "C"

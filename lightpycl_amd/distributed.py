@@ -156,6 +156,14 @@ def shard_bounds(n, rank, world):
     return lo, lo + q + (1 if rank < r else 0)
 
 
+def emit_shard(n, rank, world):
+    """(first, count) of `rank`'s shard_bounds, as ``light_source(..., on_device=True,
+    shard=...)`` takes it: the rank emits its own rays of the n-ray source on its
+    GPU (every rank from the same np.random state), with no host arrays and no scatter."""
+    lo, hi = shard_bounds(n, rank, world)
+    return lo, hi - lo
+
+
 class ShardedTrace:
     """Drive one rank's engine through the reference's iteration loop with global
     termination decisions.

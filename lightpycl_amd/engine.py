@@ -145,6 +145,46 @@ def select_device(device_name=None, names=None) -> int:
     return dflt
 
 
+class DeviceRays:
+    """A device-resident source (``lpc_rays``): made by :meth:`Engine.emit_hemisphere`
+    / :meth:`Engine.emit_collimated`, freed with the object.  ``n`` rays on GPU
+    ``device``; ``power_sum`` is the float64 sum of their powers."""
+
+    def __init__(self, engine, r):
+        self.engine, self.r = engine, r
+        self.device = engine.device
+        n, s = ctypes.c_int64(0), ctypes.c_double(0.0)
+        check(engine.L.lpc_rays_info(r, ctypes.byref(n), ctypes.byref(s)), engine.h)
+        self.n, self.power_sum = n.value, s.value
+
+    def rotate(self, R, pivot):
+        """lpc_rays_rotate: (origin - pivot) . R + pivot, dir . R."""
+        R9 = Engine._mat9(R)
+        piv = np.zeros(4, np.float64)
+        p = np.asarray(pivot, np.float64).reshape(-1)[:4]
+        piv[:p.size] = p
+        check(self.engine.L.lpc_rays_rotate(self.engine.h, self.r, ptr(R9), ptr(piv)), self.engine.h)
+
+    def fetch(self, origin=True, dirs=True, power=True):
+        """-> (origin (n,4), dir (n,4), power (n,)) float32 host copies (None where not asked)."""
+        o = np.empty((self.n, 4), np.float32) if origin else None
+        d = np.empty((self.n, 4), np.float32) if dirs else None
+        p = np.empty(self.n, np.float32) if power else None
+        check(self.engine.L.lpc_rays_fetch(self.engine.h, self.r, ptr(o), ptr(d), ptr(p)), self.engine.h)
+        return o, d, p
+
+    def free(self):
+        if getattr(self, "r", None):
+            self.engine.L.lpc_rays_free(self.r)
+            self.r = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Engine:
     """A liblpc handle on one GPU (HIP device ordinal ``device``)."""
 
@@ -275,6 +315,61 @@ class Engine:
             if staged:
                 staged.pop(0)               # the helper has copied it (joined in the call)
         return type(arr).from_buffer_copy(arr)[:k.value], (c.value, mp[: self.mesh_count].copy())
+
+    # -- light sources born on the device ---------------------------------------
+    @staticmethod
+    def _mt_state(key, pos):
+        key = np.array(key, dtype=np.uint32).reshape(-1)        # a copy: advanced in place
+        if key.size != 624:
+            raise ValueError("an MT19937 key has 624 words")
+        return key, ctypes.c_int32(int(pos))
+
+    def rng_mt19937(self, key, pos, n, skip=False):
+        """lpc_rng_mt19937: the next ``n`` doubles of numpy's legacy stream whose
+        state is (key, pos) = np.random.get_state()[1:3], generated on the GPU.
+        -> (doubles (n,) float64, or None with ``skip``; advanced key; advanced pos)."""
+        key, p = self._mt_state(key, pos)
+        out = None if skip else np.empty(int(n), np.float64)
+        self._c(self.L.lpc_rng_mt19937(self.h, ptr(key), ctypes.byref(p), int(n), ptr(out)))
+        return out, key, p.value
+
+    @staticmethod
+    def _mat9(M):
+        return np.ascontiguousarray(np.asarray(M, np.float64)[:3, :3]).reshape(9)
+
+    def emit_hemisphere(self, key, pos, n, center, Rx, Rz, power=1.0, m=1.0, first=0, count=None):
+        """lpc_rays_emit_hemisphere -> (DeviceRays, advanced key, advanced pos).
+        ``Rx`` / ``Rz``: light_source._Rx(elev0) / _Rz(az0) (3x3 or the 4x4 matrices)."""
+        key, p = self._mt_state(key, pos)
+        c4 = f32(center).reshape(-1)[:4].copy()
+        rx, rz = self._mat9(Rx), self._mat9(Rz)
+        out = ctypes.c_void_p()
+        self._c(self.L.lpc_rays_emit_hemisphere(self.h, ptr(key), ctypes.byref(p), int(n), int(first),
+                                                int(n - first if count is None else count), ptr(c4), ptr(rx),
+                                                ptr(rz), float(power), float(m), ctypes.byref(out)))
+        return DeviceRays(self, out), key, p.value
+
+    def emit_collimated(self, key, pos, n, diameter, center, Rx, Rz, dir_row, power=1.0, first=0, count=None):
+        """lpc_rays_emit_collimated -> (DeviceRays, advanced key, advanced pos)."""
+        key, p = self._mt_state(key, pos)
+        c4 = f32(center).reshape(-1)[:4].copy()
+        rx, rz = self._mat9(Rx), self._mat9(Rz)
+        d3 = f32(dir_row).reshape(-1)[:3].copy()
+        out = ctypes.c_void_p()
+        self._c(self.L.lpc_rays_emit_collimated(self.h, ptr(key), ctypes.byref(p), int(n), int(first),
+                                                int(n - first if count is None else count), float(diameter),
+                                                ptr(c4), ptr(rx), ptr(rz), ptr(d3), float(power),
+                                                ctypes.byref(out)))
+        return DeviceRays(self, out), key, p.value
+
+    def set_rays_dev(self, sources, max_ray_len=1e3, ior_env=1.0):
+        """lpc_trace_set_rays_dev: the DeviceRays of ``sources``, concatenated in
+        list order on the device, become the emitted rays.  -> their ray count."""
+        sources = list(sources)
+        arr = (ctypes.c_void_p * max(len(sources), 1))(*[s.r for s in sources])
+        self._c(self.L.lpc_trace_set_rays_dev(self.h, arr, len(sources), np.float32(max_ray_len),
+                                              np.float32(ior_env)))
+        return sum(s.n for s in sources)
 
     def reset(self):
         self._c(self.L.lpc_trace_reset(self.h))

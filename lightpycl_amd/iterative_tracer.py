@@ -154,6 +154,11 @@ class CL_Tracer:
         clk = time.perf_counter
         ph = {}                                 # host-side phases of this call (self.phase_s)
         t_ph = clk()
+        dev = None if keep_results else self._device_sources(light_source)
+        if dev is not None:
+            return self._trace_device_sources(dev, meshes, trace_iterations, trace_until_dissipated, max_ray_len,
+                                              ior_env)
+        # every other case reads the sources' host arrays (a device source fetches them)
         origin = dirs = power = None
         # results mode keeps iteration 0's origins in its results tuple: a copy, as
         # the reference's np.float32(...) is; aggregate mode only reads them
@@ -241,6 +246,63 @@ class CL_Tracer:
             t_ph = clk()
         finally:
             self.engine.sync()                  # the exported results arrays are complete
+        ph["sync"] = clk() - t_ph
+        self.phase_s = ph
+        self.sim_time = time.time() - t0
+        return self.results
+
+    def _device_sources(self, light_source):
+        """The sources' DeviceRays when every source of the list lives on this
+        tracer's GPU (light_source(on_device=True)), else None."""
+        if not isinstance(light_source, (list, tuple)) or not light_source:
+            return None
+        dev = [getattr(s, "__dict__", {}).get("_dev") for s in light_source]
+        if any(r is None or r.device != self.engine.device for r in dev):
+            return None
+        return dev
+
+    def _trace_device_sources(self, dev, meshes, trace_iterations, trace_until_dissipated, max_ray_len, ior_env):
+        """Aggregate mode on device sources: no ray crosses PCIe.  The input power
+        of the stop threshold (:115, :383) is the sources' float64 device sums
+        added in list order, not the reference's float32 sorted sum: the same kind
+        of last-bits deviation as the float64 power left of this mode."""
+        clk = time.perf_counter
+        ph = {}
+        t_ph = clk()
+        arrs = self._flatten(meshes)                                   # :121-151
+        ph["flatten"] = clk() - t_ph
+        t_ph = clk()
+        self.engine.upload_arrays(*arrs)
+        self.tri_count = np.int32(arrs[0].shape[0])
+        self.meshes = meshes
+        self.geometry = (arrs[0], arrs[1], arrs[2])
+        ph["scene"] = clk() - t_ph
+        t_ph = clk()
+        self.engine.set_rays_dev(dev, max_ray_len, ior_env)
+        ph["set_rays"] = clk() - t_ph
+        t_ph = clk()
+        input_power = 0.0
+        for r in dev:
+            input_power += r.power_sum
+        self.results = []
+        self.iteration_counts = []
+        self.power_left = []
+        self._aggregate = True
+        self.exact_sums = 0
+        thr = (1.0 - trace_until_dissipated) * input_power              # :383
+        t0 = time.time()
+        try:
+            stats, _ = self.engine.run_local(int(trace_iterations), float(thr), wait=False)
+            for t_iter, st in enumerate(stats):
+                self.iteration_counts.append(int(st.n_in))
+                self.power_left.append(float(st.power_next) / float(input_power) if input_power else 0.0)
+                if self.verbose:
+                    print(f"iteration {t_iter + 1}: {st.n_in} rays, {st.n_reflect + st.n_refract} children "
+                          f"kept, {100.0 * self.power_left[-1]:.4f} % power left")
+            ph["loop"] = clk() - t_ph
+            t_ph = clk()
+        finally:
+            self.engine.sync()
         ph["sync"] = clk() - t_ph
         self.phase_s = ph
         self.sim_time = time.time() - t0
