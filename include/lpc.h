@@ -377,6 +377,28 @@ int lpc_rays_free(lpc_rays *r);
  * read and may be freed or traced again afterwards. */
 int lpc_trace_set_rays_dev(lpc_handle *h, lpc_rays *const *list, int32_t count, float max_ray_len, float ior_env);
 
+/* ---- per-ray power cutoff ------------------------------------------------- */
+/* Opt-in (default 0 = off: every result keeps the bits it has without it).  With
+ * min_power > 0 a child ray that the compaction would keep is culled iff
+ * fabsf(child power) < min_power (float32 compare on the power as the shading
+ * wrote it; NaN is never culled, negative powers count by magnitude).  A culled
+ * child is treated as terminated: not in the next population, n_reflect /
+ * n_refract, power_next / power_nonneg, nor seen by the stop rule.  Emitted rays
+ * are never culled and the current iteration's results tuple is unchanged.
+ * Applies to every trace path (lpc_trace_iterate*, lpc_trace_run*, staged and
+ * device sources), not to the per-kernel drop-ins (lpc_bounce_host,
+ * lpc_intersect*, lpc_reflect_refract_rays).  Holds until changed, from the next
+ * launched iteration.  LPC_E_ARG for a negative, NaN or infinite value. */
+int lpc_trace_set_min_power(lpc_handle *h, float min_power);
+/* The culled-power ledger of the current trace: per iteration the number of
+ * culled children and the float64 sum of their float32 powers (fixed summation
+ * order: two runs give the same bits).  Cleared wherever the measured record is
+ * (set_rays, reset, rerun, run_staged, set_rays_dev).  *n_iter: iterations since
+ * then; at most cap entries are copied.  Waits for the stream.  The ledger
+ * holds 16 384 iterations: with a cutoff set, an iteration past that fails with
+ * LPC_E_STATE. */
+int lpc_trace_culled(lpc_handle *h, int64_t *count, double *power, int32_t cap, int32_t *n_iter);
+
 /* ---- diagnostics ---------------------------------------------------------- */
 /* The device's own conservative-filter code on n (ray, record) pairs, host
  * arrays: origin3/dir3 (n,3), rec5 (n,5) = centre xyz, negB, negA (filter_record /

@@ -113,6 +113,8 @@ _PROTOS = {
     "lpc_rays_fetch": [_P, _P, _P, _P, _P],
     "lpc_rays_free": [_P],
     "lpc_trace_set_rays_dev": [_P, _P, _I32, _F32, _F32],
+    "lpc_trace_set_min_power": [_P, _F32],
+    "lpc_trace_culled": [_P, _P, _P, _I32, _P],
 }
 
 # lpc_allreduce_fn (include/lpc.h): int (*)(void *ctx, double *vals, int32_t n)

@@ -186,6 +186,11 @@ struct CompactArgs {
     int32_t *mm;
     DevAcc *host_acc;                 // mapped pinned host copy k_scan publishes (or NULL)
     unsigned int seq;                 // ... with this sequence number, written last
+    // power cutoff (k_count<true> / k_scatter<true> only): a kept child with
+    // |power| < cut is dropped; the tile's culled count and power go to the ledger
+    float cut;
+    uint32_t *blk_cc;                 // [nb] culled children
+    double *blk_cp;                   // [nb] their power (float64 sum, per-ray order)
 };
 
 // Two-kernel compaction of a traced single-chunk iteration (k_shade_stage ->
@@ -223,6 +228,25 @@ struct StageArgs {
     uint32_t *tmask;                  // the walk's written-slot masks (only those slots are read), or NULL
     uint32_t *tbox;                   // [ntiles][6] box of the tile's kept children origins (ord_f32 min xyz,
                                       //   max xyz), or NULL: the next population's coherence key box
+    // power cutoff (the CUT instantiations only): see CompactArgs
+    float cut;
+    uint32_t *tcc;                    // [ntiles] culled children
+    double *tcp;                      // [ntiles] their power
+};
+// The culled-power ledger (lpc_trace_culled): one slot per iteration of the
+// trace, written by k_cull_sum after the iteration's compaction.
+struct CullSlot {
+    long long count;
+    double power;
+};
+struct CullSumArgs {
+    const uint32_t *cc;               // per-tile culled counts / powers of one launch
+    const double *cp;
+    int64_t ntiles;
+    const long long *nd;              // device-sized launch: the rays, ntiles = ceil(*nd / tile)
+    int tile;
+    CullSlot *slot;                   // the iteration's slot
+    int first;                        // first chunk of the iteration: write (later chunks add, chunk order)
 };
 #define LPC_ST_GROUP 256                  // tiles per count group (k_stage_move prefixes: groups, then tiles)
 __host__ __device__ inline unsigned long long gsum_pack(uint32_t r, uint32_t t, uint32_t m)

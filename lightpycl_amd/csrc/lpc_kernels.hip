@@ -1543,11 +1543,18 @@ static __device__ __forceinline__ float wave_max(float v)
     return v;
 }
 
+// CUT: the power cutoff's instantiation (power_culled children are not kept; the
+// tile's culled count and power go to blk_cc / blk_cp).
+template <bool CUT>
 __global__ __launch_bounds__(256) void k_count(CompactArgs A)
 {
     __shared__ int32_t s_cnt[3][4];
     __shared__ double s_pow[4];
     __shared__ float s_dm[4];
+    __shared__ int32_t s_cc[4];
+    __shared__ double s_cp[4];
+    int32_t cC = 0;
+    double pc = 0.0;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t tile = (int64_t)blockIdx.x * 1024;
     int32_t cR = 0, cT = 0, cM = 0;
@@ -1557,7 +1564,12 @@ __global__ __launch_bounds__(256) void k_count(CompactArgs A)
     for (int sub = 0; sub < 4; ++sub) {
         const int64_t r = tile + sub * 256 + threadIdx.x;
         if (r < A.n) {
-            const bool fR = A.o.rms[r] == 0, fT = A.o.tms[r] == 0, fM = A.o.meas[r] == 1;
+            bool fR = A.o.rms[r] == 0, fT = A.o.tms[r] == 0;
+            const bool fM = A.o.meas[r] == 1;
+            if constexpr (CUT) {
+                if (fR && lpc::power_culled(A.o.rpw[r], A.cut)) { fR = false; ++cC; pc += (double)A.o.rpw[r]; }
+                if (fT && lpc::power_culled(A.o.tpw[r], A.cut)) { fT = false; ++cC; pc += (double)A.o.tpw[r]; }
+            }
             cR += fR; cT += fT; cM += fM;
             neg = neg || (fR && !(A.o.rpw[r] >= 0.0f)) || (fT && !(A.o.tpw[r] >= 0.0f));
             if (fR) {
@@ -1576,6 +1588,11 @@ __global__ __launch_bounds__(256) void k_count(CompactArgs A)
     }
     pk = wave_sum(pk);
     dm = wave_max(dm);
+    if constexpr (CUT) {
+        for (int o = 32; o >= 1; o >>= 1) cC += __shfl_xor(cC, o, 64);
+        pc = wave_sum(pc);
+        if (lane == 0) { s_cc[wv] = cC; s_cp[wv] = pc; }
+    }
     if (any_lane(neg) && lane == 0) atomicOr(&A.acc->pneg, 1u);
     if (lane == 0) {
         s_cnt[0][wv] = cR; s_cnt[1][wv] = cT; s_cnt[2][wv] = cM; s_pow[wv] = pk; s_dm[wv] = dm;
@@ -1583,6 +1600,10 @@ __global__ __launch_bounds__(256) void k_count(CompactArgs A)
     __syncthreads();
     if (threadIdx.x == 0) {
         const int64_t b = blockIdx.x, nb = A.nb;
+        if constexpr (CUT) {
+            A.blk_cc[b] = (uint32_t)(s_cc[0] + s_cc[1] + s_cc[2] + s_cc[3]);
+            A.blk_cp[b] = ((s_cp[0] + s_cp[1]) + s_cp[2]) + s_cp[3];
+        }
         A.blk_cnt[0 * nb + b] = s_cnt[0][0] + s_cnt[0][1] + s_cnt[0][2] + s_cnt[0][3];
         A.blk_cnt[1 * nb + b] = s_cnt[1][0] + s_cnt[1][1] + s_cnt[1][2] + s_cnt[1][3];
         A.blk_cnt[2 * nb + b] = s_cnt[2][0] + s_cnt[2][1] + s_cnt[2][2] + s_cnt[2][3];
@@ -1671,6 +1692,7 @@ __global__ __launch_bounds__(1024) void k_scan(CompactArgs A)
     }
 }
 
+template <bool CUT>
 __global__ __launch_bounds__(256) void k_scatter(CompactArgs A)
 {
     __shared__ int32_t s_w[3][4];
@@ -1682,9 +1704,13 @@ __global__ __launch_bounds__(256) void k_scatter(CompactArgs A)
     for (int sub = 0; sub < 4; ++sub) {
         const int64_t r = tile + sub * 256 + threadIdx.x;
         const bool in = r < A.n;
-        const bool fR = in && A.o.rms[r] == 0;
-        const bool fT = in && A.o.tms[r] == 0;
+        bool fR = in && A.o.rms[r] == 0;
+        bool fT = in && A.o.tms[r] == 0;
         const bool fM = in && A.o.meas[r] == 1;
+        if constexpr (CUT) {             // the same decision as k_count<true>
+            fR = fR && !lpc::power_culled(A.o.rpw[r], A.cut);
+            fT = fT && !lpc::power_culled(A.o.tpw[r], A.cut);
+        }
         const uint64_t bR = __ballot(fR), bT = __ballot(fT), bM = __ballot(fM);
         const uint64_t below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
         const int pR = __popcll(bR & below), pT = __popcll(bT & below), pM = __popcll(bM & below);
@@ -1734,7 +1760,11 @@ __global__ __launch_bounds__(256) void k_scatter(CompactArgs A)
 //                  sum) and publishes them to the host.
 // Children and measured rays land at the same positions as with the four
 // kernels ([reflected ; refracted], each in parent order).
-template <int KU, bool DS>
+// CUT: the power cutoff's instantiation (lpc_trace_set_min_power): a kept child
+// with |power| < cut is dropped here, before anything counts it; the tile's culled
+// count and power (tcc / tcp) feed the ledger (k_cull_sum).  Its extra wave sums
+// and per-tile arrays exist only in that instantiation.
+template <int KU, bool DS, bool CUT = false>
 __global__ __launch_bounds__(LPC_ST_TILE) void k_shade_stage(StageArgs A)
 {
     __shared__ double s_mp[LPC_MP_MAX][LPC_ST_TILE / 64];
@@ -1742,6 +1772,8 @@ __global__ __launch_bounds__(LPC_ST_TILE) void k_shade_stage(StageArgs A)
     __shared__ double s_pow[LPC_ST_TILE / 64];
     __shared__ float s_dm[LPC_ST_TILE / 64];
     __shared__ uint32_t s_bx[LPC_ST_TILE / 64][6];
+    __shared__ int32_t s_cc[CUT ? LPC_ST_TILE / 64 : 1];
+    __shared__ double s_cp[CUT ? LPC_ST_TILE / 64 : 1];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     // the shading inputs as a local (a device-sized launch sets its n; writing the
     // kernel argument itself would put the whole argument block in scratch)
@@ -1782,7 +1814,21 @@ __global__ __launch_bounds__(LPC_ST_TILE) void k_shade_stage(StageArgs A)
             if (A.scnt[a] != 0) A.scnt[a] = 0;
         }
     }
-    const bool fR = in && s.r_meas == 0, fT = in && s.t_meas == 0, fM = in && s.meas == 1;
+    bool fR = in && s.r_meas == 0, fT = in && s.t_meas == 0;
+    const bool fM = in && s.meas == 1;
+    if constexpr (CUT) {
+        // culled children (per-ray order: reflected, then refracted; waves, then
+        // tiles and chunks in order: the ledger's float64 sum is deterministic)
+        const bool uR = fR && lpc::power_culled(s.r_pow, A.cut), uT = fT && lpc::power_culled(s.t_pow, A.cut);
+        double pc = 0.0;
+        if (uR) pc += (double)s.r_pow;
+        if (uT) pc += (double)s.t_pow;
+        pc = wave_sum(pc);
+        const int cc = __popcll(__ballot(uR)) + __popcll(__ballot(uT));
+        if (lane == 0) { s_cc[wv] = cc; s_cp[wv] = pc; }
+        fR = fR && !uR;
+        fT = fT && !uT;
+    }
     const uint64_t bR = __ballot(fR), bT = __ballot(fT), bM = __ballot(fM);
     const uint64_t below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     // kept power and max |dir|^2 (k_count's per-ray order: reflected, then refracted)
@@ -1849,6 +1895,13 @@ __global__ __launch_bounds__(LPC_ST_TILE) void k_shade_stage(StageArgs A)
         A.tcnt[tile] = cR | (cT << 9) | (cM << 18);
         A.tpow[tile] = tp;
         A.tdm[tile] = __float_as_uint(td);
+        if constexpr (CUT) {
+            uint32_t cc = 0;
+            double cp = 0.0;
+            for (int k = 0; k < LPC_ST_TILE / 64; ++k) { cc += (uint32_t)s_cc[k]; cp += s_cp[k]; }
+            A.tcc[tile] = cc;
+            A.tcp[tile] = cp;
+        }
         if (A.tbox) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
@@ -2186,6 +2239,40 @@ __global__ __launch_bounds__(256) void k_append(RaysOut dst, RaysIn src, const D
         dst.ox[q] = src.ox[i]; dst.oy[q] = src.oy[i]; dst.oz[q] = src.oz[i];
         dst.dx[q] = src.dx[i]; dst.dy[q] = src.dy[i]; dst.dz[q] = src.dz[i];
         dst.pw[q] = src.pw[i]; dst.pmid[q] = src.pmid[i];
+    }
+}
+
+// The culled-power ledger's slot of one iteration: the launch's per-tile culled
+// counts and powers summed in a fixed order (a thread's tiles in tile order, then
+// a tree over the threads).  The first chunk of an iteration writes the slot --
+// never accumulated, so an iteration that is re-run overwrites it, and a
+// device-sized iteration that ran empty leaves zeros -- later chunks add in
+// chunk order.
+__global__ __launch_bounds__(256) void k_cull_sum(CullSumArgs A)
+{
+    __shared__ long long s_c[256];
+    __shared__ double s_p[256];
+    const int t = threadIdx.x;
+    int64_t nt = A.ntiles;
+    if (A.nd) {
+        const long long n = *A.nd;
+        nt = n > 0 ? min((int64_t)((n + A.tile - 1) / A.tile), A.ntiles) : 0;
+    }
+    const int64_t per = (nt + 255) / 256;
+    const int64_t lo = min((int64_t)t * per, nt), hi = min(lo + per, nt);
+    long long c = 0;
+    double p = 0.0;
+    for (int64_t j = lo; j < hi; ++j) { c += A.cc[j]; p += A.cp[j]; }
+    s_c[t] = c; s_p[t] = p;
+    for (int off = 128; off >= 1; off >>= 1) {
+        __syncthreads();
+        if (t < off) { s_c[t] += s_c[t + off]; s_p[t] += s_p[t + off]; }
+    }
+    if (t == 0) {
+        CullSlot v;
+        v.count = s_c[0]; v.power = s_p[0];
+        if (!A.first) { v.count += A.slot->count; v.power = A.slot->power + v.power; }
+        *A.slot = v;
     }
 }
 

@@ -40,6 +40,12 @@ LPC_HD f3 add3(f3 a, f3 b) { LPC_EXACT return mk3(a.x + b.x, a.y + b.y, a.z + b.
 LPC_HD f3 sub3(f3 a, f3 b) { LPC_EXACT return mk3(a.x - b.x, a.y - b.y, a.z - b.z); }
 LPC_HD f3 scl3(f3 a, float s) { LPC_EXACT return mk3(a.x * s, a.y * s, a.z * s); }
 LPC_HD f3 neg3(f3 a) { return mk3(-a.x, -a.y, -a.z); }
+// The per-ray power cutoff (lpc_trace_set_min_power): a
+// child the compaction would keep is dropped iff |power| < cut, compared in
+// float32 on the power as the shading wrote it.  cut = 0 never culls, a NaN
+// power is never culled (the comparison is false), negative powers count by
+// magnitude.  Every compaction site uses this one predicate.
+LPC_HD bool power_culled(float child_pow, float cut) { return fabsf(child_pow) < cut; }
 // OpenCL's geometric builtins for float3 exactly as ROCm's OpenCL device library
 // (the library the reference's kernels link when built for an AMD GPU,
 // oracle/Makefile `ref`) evaluates them: dot = fma(z, z', fma(y, y', x x')),

@@ -74,6 +74,7 @@ struct PieceTable {
 const int kShadeF = 12;   // float arrays of the shade outputs
 const int kShadeI = 8;    // int arrays
 const int kAccRing = 8;   // mapped counter slots (iterations in flight: at most 2)
+const int64_t kCullSlots = 16384;   // iterations the culled-power ledger holds (256 KB on the device)
 
 // Launch policy.  Each value won its A/B (DESIGN.md sections 5 and 7; the losing
 // alternatives and their knobs were removed in round 5, the tables there keep the
@@ -237,6 +238,12 @@ struct lpc_handle {
     DBuf w_tbox, d_pbox;                            // per-tile boxes (k_shade_stage), the population's box (k_stage_move)
     bool pbox_ok = false;                           // d_pbox holds the current population's origin box
     double mp_last[LPC_MP_MAX] = {0, 0, 0, 0};
+    // per-ray power cutoff (lpc_trace_set_min_power) and its ledger (lpc_trace_culled)
+    float min_power = 0.0f;                         // 0: off (the default instantiations of the compaction kernels)
+    DBuf d_cull;                                    // CullSlot[kCullSlots]: one per iteration of the trace
+    DBuf w_cull;                                    // per-tile culled counts / powers of one launch
+    bool cull_dirty = false;                        // some slot may be non-zero (cleared with the measured record)
+    int64_t it_done = 0;                            // iterations collected since the trace's reset
     // trace
     Pop A, B, T, I;
     int64_t n_cur = 0, n_init = 0;
@@ -336,6 +343,16 @@ static int set_err(lpc_handle *h, int code, const std::string &msg)
         else if (K_ <= 12) hipLaunchKernelGGL((KERN<12, B>), grid, block, 0, stream, __VA_ARGS__); \
         else if (K_ <= 16) hipLaunchKernelGGL((KERN<16, B>), grid, block, 0, stream, __VA_ARGS__); \
         else hipLaunchKernelGGL((KERN<0, B>), grid, block, 0, stream, __VA_ARGS__);              \
+    } while (0)
+
+#define LPC_KU_LAUNCH3(h, KERN, B, C, grid, block, stream, ...)                                      \
+    do {                                                                                            \
+        const int K_ = (h)->K;                                                                      \
+        if (K_ <= 4) hipLaunchKernelGGL((KERN<4, B, C>), grid, block, 0, stream, __VA_ARGS__);      \
+        else if (K_ <= 8) hipLaunchKernelGGL((KERN<8, B, C>), grid, block, 0, stream, __VA_ARGS__); \
+        else if (K_ <= 12) hipLaunchKernelGGL((KERN<12, B, C>), grid, block, 0, stream, __VA_ARGS__); \
+        else if (K_ <= 16) hipLaunchKernelGGL((KERN<16, B, C>), grid, block, 0, stream, __VA_ARGS__); \
+        else hipLaunchKernelGGL((KERN<0, B, C>), grid, block, 0, stream, __VA_ARGS__);              \
     } while (0)
 
 // Wait for a trace's kernels still queued on the stream: lpc_trace_iterate and
@@ -1417,7 +1434,7 @@ int lpc_close(lpc_handle *h)
                     &h->w_stage, &h->w_sort, &h->w_sort_tmp, &h->w_bhist, &h->d_srec, &h->A.buf, &h->B.buf, &h->T.buf, &h->I.buf, &h->m_buf,
                     &h->d_acc, &h->d_tmp, &h->d_scan, &h->d_stats, &h->d_misc, &h->w_spill, &h->w_qroots,
                     &h->w_aos, &h->w_fc, &h->d_mrun, &h->w_gsum, &h->d_ctl, &h->d_cbase, &h->w_tbox, &h->d_pbox,
-                    &h->d_mt, &h->d_rng, &h->d_etile};
+                    &h->d_mt, &h->d_rng, &h->d_etile, &h->d_cull, &h->w_cull};
     for (DBuf *b : bufs) dfree(*b);
     if (h->acc_host) (void)hipHostFree(h->acc_host);
     h->acc_host = nullptr;
@@ -1993,6 +2010,13 @@ int lpc_trace_reset(lpc_handle *h)
     h->pbox_ok = false;
     h->m_total = 0;                             // measured record emptied (the first iteration resets the counters)
     h->m_inflight = 0;
+    // the culled-power ledger goes with the measured record (stream-ordered:
+    // behind whatever an earlier trace still runs)
+    h->it_done = 0;
+    if (h->cull_dirty && h->d_cull.p) {
+        HIPCHK(h, hipMemsetAsync(h->d_cull.p, 0, h->d_cull.bytes, h->stream));
+        h->cull_dirty = false;
+    }
     return 0;
 }
 
@@ -2260,6 +2284,40 @@ int lpc_trace_global_stats(lpc_handle *h, lpc_iter_stats *per_iter, int32_t cap,
     return 0;
 }
 
+int lpc_trace_set_min_power(lpc_handle *h, float min_power)
+{
+    if (!(min_power >= 0.0f) || !std::isfinite(min_power))
+        return set_err(h, LPC_E_ARG, "set_min_power: the cutoff must be finite and >= 0");
+    if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
+    if (min_power != h->min_power) {
+        // a prediction made under another cutoff is not reused
+        h->hist_r.clear();
+        h->hist_iter = -1;
+    }
+    h->min_power = min_power;           // from the next launched iteration
+    return 0;
+}
+
+int lpc_trace_culled(lpc_handle *h, int64_t *count, double *power, int32_t cap, int32_t *n_iter)
+{
+    if (!h || !n_iter) return set_err(h, LPC_E_ARG, "null argument");
+    if (cap < 0 || (cap > 0 && (!count || !power))) return set_err(h, LPC_E_ARG, "trace_culled: missing buffer");
+    RETIF(settle(h));
+    const int64_t n = std::min<int64_t>(h->it_done, kCullSlots);
+    *n_iter = (int32_t)n;
+    const int64_t m = std::min<int64_t>(n, cap);
+    for (int64_t i = 0; i < m; ++i) { count[i] = 0; power[i] = 0.0; }
+    if (m > 0 && h->d_cull.p) {
+        HIPCHK(h, hipSetDevice(h->device));
+        std::vector<CullSlot> v((size_t)m);
+        HIPCHK(h, hipMemcpyAsync(v.data(), h->d_cull.p, (size_t)m * sizeof(CullSlot), hipMemcpyDeviceToHost,
+                                 h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (int64_t i = 0; i < m; ++i) { count[i] = (int64_t)v[(size_t)i].count; power[i] = v[(size_t)i].power; }
+    }
+    return 0;
+}
+
 int lpc_shm_comm_open(const char *name, int32_t rank, int32_t world, int32_t create, lpc_shm_comm **out)
 {
     if (!out) return set_err(nullptr, LPC_E_ARG, "shm comm: null output");
@@ -2474,6 +2532,28 @@ static int iter_enqueue(lpc_handle *h, float *out_origin4, float *out_dest4, flo
     if (!ds) RETIF(pop_reserve(h, h->T, N));
     // measured rows: the iterations still in flight may append up to their populations
     RETIF(ensure_measured(h, h->m_total + h->m_inflight + N));
+    // power cutoff: the compaction's CUT instantiations, this launch's per-tile
+    // culled sums and the iteration's ledger slot (a device-sized iteration is
+    // enqueued while the iteration before it is uncollected: the slot after its)
+    const bool cut = h->min_power > 0.0f;
+    CullSumArgs CS;
+    memset(&CS, 0, sizeof(CS));
+    if (cut) {
+        const int64_t slot = h->it_done + (ds ? 1 : 0);
+        if (slot >= kCullSlots)
+            return set_err(h, LPC_E_STATE, "trace: the culled-power ledger holds " + std::to_string(kCullSlots) +
+                                               " iterations");
+        if (!h->d_cull.p) {
+            RETIF(dalloc(h, h->d_cull, (size_t)kCullSlots * sizeof(CullSlot)));
+            HIPCHK(h, hipMemsetAsync(h->d_cull.p, 0, h->d_cull.bytes, h->stream));
+        }
+        const size_t nt_ws = ((size_t)h->ws_rays + LPC_ST_TILE - 1) / LPC_ST_TILE;
+        RETIF(dalloc(h, h->w_cull, nt_ws * (8 + 4) + 64));
+        CS.cp = (const double *)h->w_cull.p;
+        CS.cc = (const uint32_t *)(CS.cp + nt_ws);
+        CS.slot = (CullSlot *)h->d_cull.p + slot;
+        h->cull_dirty = true;
+    }
     if (h->host_prof)
         fprintf(stderr, "[lpc host]   buffers %.1f us (m_total %lld inflight %lld m_cap %lld)\n", host_us() - hp0,
                 (long long)h->m_total, (long long)h->m_inflight, (long long)h->m_cap);
@@ -2537,6 +2617,8 @@ static int iter_enqueue(lpc_handle *h, float *out_origin4, float *out_dest4, flo
         A.mm = (int32_t *)(mf + 4 * mc);
         A.host_acc = early ? h->acc_map_dev + P->seq % kAccRing : nullptr;
         A.seq = P->seq;
+        A.cut = h->min_power; A.blk_cc = (uint32_t *)CS.cc; A.blk_cp = (double *)CS.cp;
+        CS.first = base == 0 ? 1 : 0;
         if (fused) {                  // shade + staged compaction, two kernels (k_shade_stage, k_stage_move)
             // device-sized: grid from the expected size (grid-stride over the actual tiles)
             const int64_t ng_rays = ds ? std::max<int64_t>(1, std::min(ds->pred, nc)) : nc;
@@ -2565,8 +2647,12 @@ static int iter_enqueue(lpc_handle *h, float *out_origin4, float *out_dest4, flo
             // the children's origin box when they may be re-sorted (population >= LPC_RESORT_MIN)
             const bool want_box = !ds && 2 * N >= h->resort_min;
             G.tbox = want_box ? (uint32_t *)h->w_tbox.p : nullptr;
+            G.cut = h->min_power; G.tcc = A.blk_cc; G.tcp = A.blk_cp;
 
-            if (ds) LPC_KU_LAUNCH2(h, k_shade_stage, true, dim3((unsigned)nt), dim3(LPC_ST_TILE), h->stream, G);
+            if (cut) {
+                if (ds) LPC_KU_LAUNCH3(h, k_shade_stage, true, true, dim3((unsigned)nt), dim3(LPC_ST_TILE), h->stream, G);
+                else LPC_KU_LAUNCH3(h, k_shade_stage, false, true, dim3((unsigned)nt), dim3(LPC_ST_TILE), h->stream, G);
+            } else if (ds) LPC_KU_LAUNCH2(h, k_shade_stage, true, dim3((unsigned)nt), dim3(LPC_ST_TILE), h->stream, G);
             else LPC_KU_LAUNCH2(h, k_shade_stage, false, dim3((unsigned)nt), dim3(LPC_ST_TILE), h->stream, G);
             MoveArgs M;
             M.ntiles = nt_max;
@@ -2611,6 +2697,10 @@ static int iter_enqueue(lpc_handle *h, float *out_origin4, float *out_dest4, flo
             P->mp_fused = G.nmp > 0 || h->meas_meshes.empty();
             if (ds) hipLaunchKernelGGL(k_stage_move<true>, dim3((unsigned)nt), dim3(LPC_ST_TILE), 0, h->stream, M);
             else hipLaunchKernelGGL(k_stage_move<false>, dim3((unsigned)nt), dim3(LPC_ST_TILE), 0, h->stream, M);
+            if (cut) {                          // the ledger, off the counters' publication
+                CS.ntiles = nt_max; CS.tile = LPC_ST_TILE; CS.nd = ds ? ds->nd : nullptr;
+                hipLaunchKernelGGL(k_cull_sum, dim3(1), dim3(256), 0, h->stream, CS);
+            }
             h->slots_clean = true;              // k_shade_stage restored what it read
             h->slots_mrl = h->max_ray_len;
             h->misc_clean = true;               // k_stage_move reset the next launch's words
@@ -2619,7 +2709,13 @@ static int iter_enqueue(lpc_handle *h, float *out_origin4, float *out_dest4, flo
             continue;
         }
         RETIF(run_shade(h, in, nullptr, nc, h->max_ray_len, h->ior_env, false));
-        hipLaunchKernelGGL(k_count, dim3((unsigned)A.nb), dim3(256), 0, h->stream, A);
+        if (cut) {
+            hipLaunchKernelGGL(k_count<true>, dim3((unsigned)A.nb), dim3(256), 0, h->stream, A);
+            CS.ntiles = A.nb; CS.tile = 1024; CS.nd = nullptr;
+            hipLaunchKernelGGL(k_cull_sum, dim3(1), dim3(256), 0, h->stream, CS);
+        } else {
+            hipLaunchKernelGGL(k_count<false>, dim3((unsigned)A.nb), dim3(256), 0, h->stream, A);
+        }
         if (X) {
             const double hx = h->host_prof ? host_us() : 0.0;
             RETIF(export_chunk(h, in, o, nc, base, N, *X));
@@ -2641,7 +2737,8 @@ static int iter_enqueue(lpc_handle *h, float *out_origin4, float *out_dest4, flo
             if (out_meas) HIPCHK(h, hipMemcpy(out_meas + base, o.meas, (size_t)nc * 4, hipMemcpyDeviceToHost));
         }
         hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, h->stream, A);
-        hipLaunchKernelGGL(k_scatter, dim3((unsigned)A.nb), dim3(256), 0, h->stream, A);
+        if (cut) hipLaunchKernelGGL(k_scatter<true>, dim3((unsigned)A.nb), dim3(256), 0, h->stream, A);
+        else hipLaunchKernelGGL(k_scatter<false>, dim3((unsigned)A.nb), dim3(256), 0, h->stream, A);
         HIPCHK(h, hipGetLastError());
         if (h->prof && !h->prof_light) { (void)hipEventRecord(e1, h->stream); h->ev_rest.push_back({e0, e1}); }
     }
@@ -2671,6 +2768,7 @@ static int iter_collect(lpc_handle *h, const Pending &P, float *out_next_pow, lp
     memset(&S, 0, sizeof(S));
     S.n_in = P.n_in;
     S.power_nonneg = 1;
+    ++h->it_done;                       // the ledger's slot count (an empty iteration's slot stays zero)
     if (P.empty) { if (st) *st = S; return 0; }
     DevAcc acc;
     const double t_wait = h->host_prof ? host_us() : 0.0;

@@ -235,6 +235,16 @@ class ShardedTrace:
             _, mesh_pow = self.engine.measured()
             mesh_pow = self._sum(np.asarray(mesh_pow, dtype=np.float64))
         out = dict(bounces=bounces, iterations=iters, global_counts=counts, mesh_power=mesh_pow)
+        if getattr(self.engine, "min_power", 0.0) > 0.0:
+            # the culled-power ledger (Engine.set_min_power, the same cutoff on every
+            # rank) summed over the ranks at the trace's end, through this object's
+            # comm (every rank ran the same number of iterations); the library's
+            # per-iteration hook and its payload are untouched
+            cc, cp = self.engine.culled()
+            k = len(cc)
+            tot = self._sum(np.concatenate((np.asarray(cc, np.float64), np.asarray(cp, np.float64))))
+            out["culled_counts"] = [int(v) for v in tot[:k]]
+            out["culled_power"] = [float(v) for v in tot[k:2 * k]]
         if hist is not None:
             limits, points = hist
             H, xe, ye = self.engine.project_hist(None, None, limits, points)[:3]

@@ -196,6 +196,7 @@ class Engine:
         self.h = h
         self.tri_count = 0
         self.mesh_count = 0
+        self.min_power = 0.0
 
     # -- lifecycle -----------------------------------------------------------
     def close(self):
@@ -370,6 +371,24 @@ class Engine:
         self._c(self.L.lpc_trace_set_rays_dev(self.h, arr, len(sources), np.float32(max_ray_len),
                                               np.float32(ior_env)))
         return sum(s.n for s in sources)
+
+    def set_min_power(self, c):
+        """lpc_trace_set_min_power: the per-ray power cutoff (float32, finite,
+        >= 0; 0 = off, the default).  A child the compaction would keep is culled
+        iff |power| < c; holds until changed, from the next launched iteration."""
+        self._c(self.L.lpc_trace_set_min_power(self.h, np.float32(c)))
+        self.min_power = float(np.float32(c))
+
+    def culled(self):
+        """lpc_trace_culled: the culled-power ledger of the current trace ->
+        (counts int64[n_iter], powers float64[n_iter]), one entry per iteration
+        since the rays were set / reset."""
+        n = ctypes.c_int32(0)
+        self._c(self.L.lpc_trace_culled(self.h, None, None, 0, ctypes.byref(n)))
+        cnt, pw = np.zeros(n.value, np.int64), np.zeros(n.value, np.float64)
+        if n.value:
+            self._c(self.L.lpc_trace_culled(self.h, ptr(cnt), ptr(pw), n.value, ctypes.byref(n)))
+        return cnt[: n.value], pw[: n.value]
 
     def reset(self):
         self._c(self.L.lpc_trace_reset(self.h))

@@ -145,12 +145,29 @@ class CL_Tracer:
         return arrs
 
     def iterative_tracer(self, light_source, meshes, trace_iterations=100, trace_until_dissipated=0.99,
-                         max_ray_len=np.float32(1e3), ior_env=np.float32(1.0), keep_results=True):
+                         max_ray_len=np.float32(1e3), ior_env=np.float32(1.0), keep_results=True,
+                         min_ray_power=0.0):
         """Trace until ``trace_iterations`` bounces, until less than
         (1 - trace_until_dissipated) of the input power is left, or until no ray is
-        left (iterative_tracer.py:241-391).  Returns ``self.results``."""
+        left (iterative_tracer.py:241-391).  Returns ``self.results``.
+
+        ``min_ray_power`` (float32, finite, >= 0; default 0 = off, the reference's
+        behaviour) is a per-ray power cutoff: a child ray that would be kept is
+        dropped iff ``|power| < min_ray_power``, as if it had been terminated.  It
+        is set on every call, so omitting the keyword turns it off.  A useful value
+        is a small fraction ``f`` of the mean emitted ray's power,
+        ``min_ray_power = f * power / ray_count`` (``f = 1e-6`` removes about three
+        quarters of the ray-bounces of the eye scene and changes its measured power
+        by 4e-8 relative).  Afterwards ``culled_counts`` / ``culled_power`` hold the
+        culled children and their float64 power sum per iteration, and
+        :meth:`power_culled` the total: with non-negative powers and passive
+        materials each measure mesh loses at most that much (DESIGN.md section
+        11).  Culled power no longer counts as power left, so a trace may stop an
+        iteration earlier than without the cutoff."""
         max_ray_len = np.float32(max_ray_len)
         ior_env = np.float32(ior_env)
+        self.engine.set_min_power(min_ray_power)
+        self.culled_counts, self.culled_power = [], []
         clk = time.perf_counter
         ph = {}                                 # host-side phases of this call (self.phase_s)
         t_ph = clk()
@@ -244,12 +261,29 @@ class CL_Tracer:
                     break
             ph["loop"] = clk() - t_ph
             t_ph = clk()
+            self._read_culled()
         finally:
             self.engine.sync()                  # the exported results arrays are complete
         ph["sync"] = clk() - t_ph
         self.phase_s = ph
         self.sim_time = time.time() - t0
         return self.results
+
+    def _read_culled(self):
+        """The trace's culled-power ledger (read only with a cutoff set: the
+        reader waits for the stream)."""
+        n = len(self.iteration_counts)
+        if self.engine.min_power > 0.0:
+            cc, cp = self.engine.culled()
+            self.culled_counts = [int(c) for c in cc[:n]]
+            self.culled_power = [float(v) for v in cp[:n]]
+        else:
+            self.culled_counts, self.culled_power = [0] * n, [0.0] * n
+
+    def power_culled(self):
+        """Total power of the children the cutoff culled in the last trace."""
+        import math
+        return math.fsum(getattr(self, "culled_power", []))
 
     def _device_sources(self, light_source):
         """The sources' DeviceRays when every source of the list lives on this
@@ -301,6 +335,7 @@ class CL_Tracer:
                           f"kept, {100.0 * self.power_left[-1]:.4f} % power left")
             ph["loop"] = clk() - t_ph
             t_ph = clk()
+            self._read_culled()
         finally:
             self.engine.sync()
         ph["sync"] = clk() - t_ph
