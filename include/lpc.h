@@ -58,6 +58,11 @@ int lpc_close(lpc_handle *h);
 const char *lpc_last_error(const lpc_handle *h);
 /* Device name / CU count of the handle's GPU (diagnostics). */
 int lpc_device_info(lpc_handle *h, char *name, int name_len, int *cu_count);
+/* Bytes of device and of pinned host memory the library holds right now, over
+ * all handles and device-resident sources of the process (either pointer may be
+ * NULL).  lpc_host_alloc blocks belong to the caller and are not counted.  A
+ * test reads it before lpc_open and after lpc_close: the two must agree. */
+int lpc_debug_live_bytes(int64_t *device_bytes, int64_t *pinned_bytes);
 
 /* ---- scene (iterative_tracer.py:121-169) -------------------------------- */
 /* Upload the flattened scene.  v0,v1,v2: host (tri_count,4) float32 rows;

@@ -63,6 +63,7 @@ _PROTOS = {
     "lpc_open": [_INT, _P],
     "lpc_close": [_P],
     "lpc_device_info": [_P, _P, _INT, _P],
+    "lpc_debug_live_bytes": [_P, _P],
     "lpc_scene_upload": [_P, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _P],
     "lpc_bounce_host": [_P, _I64, _P, _P, _P, _P, _P, _F32, _F32, _P, _P, _P, _P, _P, _P, _P,
                         _P, _P, _P, _P, _P],

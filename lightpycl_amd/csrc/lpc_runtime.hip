@@ -8,6 +8,7 @@
 #include "lpc.h"
 #include "lpc_comm.hpp"
 #include "lpc_build.hpp"
+#include "lpc_resource.hpp"
 #include <hip/hip_ext.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -24,10 +25,15 @@
 #include <thread>
 #include <limits>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
 using namespace lpck;
+using lpcr::DBuf;
+using lpcr::Event;
+using lpcr::Pinned;
+using lpcr::Stream;
 
 static double host_us()
 {
@@ -35,11 +41,6 @@ static double host_us()
 }
 
 namespace {
-
-struct DBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-};
 
 // 8 SoA arrays (ox oy oz dx dy dz pw | pmid) in one allocation.
 struct Pop {
@@ -129,9 +130,14 @@ const double kThin = 1.0;               // thin-triangle rule factor (thin_axis;
 // join events keep it (a device-scope release measured equal).
 static const unsigned kEvTimingFlags = hipEventDisableSystemFence;
 
+// Every GPU resource of the handle is held by an owner of lpc_resource.hpp and
+// goes with it; lpc_close names no member.  The one rule: members are destroyed
+// in reverse declaration order, so a stream is declared before everything that
+// may be in flight on it -- buffers and events go first, the streams last.
 struct lpc_handle {
     int device = 0;
-    hipStream_t stream = nullptr;
+    Stream stream;
+    Stream stream2;                                 // side stream: the sliver kernels beside the hierarchy stage
     std::string err;
     char name[256] = {0};
     int cus = 0;
@@ -201,9 +207,9 @@ struct lpc_handle {
     int init_key_lo = 0, init_key_hi = 32;          // key bits that vary over the emitted rays (set_rays)
     bool init_bsort = false;                        // their sort may be the counting sort (bsort_fits)
     DBuf w_qroots;                                  // root items
-    DevAcc *acc_host = nullptr;                     // pinned copy of d_acc (one read per iteration)
-    DevAcc *acc_map = nullptr, *acc_map_dev = nullptr;   // mapped pinned ring k_scan / k_stage_move publish into
-                                                    // (slot seq % kAccRing; + device address)
+    Pinned<DevAcc> acc_host;                        // pinned copy of d_acc (one read per iteration)
+    Pinned<DevAcc> acc_map;                         // mapped pinned ring k_scan / k_stage_move publish into
+    DevAcc *acc_map_dev = nullptr;                  // (slot seq % kAccRing; + device address)
     // speculative iterations (trace_run, LPC_SPEC): iteration i + 1 is enqueued
     // device-sized (IterCtl) before iteration i's counters are read
     bool spec = true;
@@ -218,18 +224,19 @@ struct lpc_handle {
     unsigned int acc_seq = 0;
     int host_prof = 0;                              // LPC_HOSTPROF: host-side timing of each iteration (stderr);
                                                     //   2: also each launch's hand-over queue lengths (synchronising)
-    hipStream_t stream2 = nullptr;                  // side stream: the sliver kernels beside the hierarchy stage
     bool side_tried = false;                        // stream2 / ev_side created on first use (side_stream)
     // results export (lpc_trace_iterate_export): k_export packs a chunk's part of
     // the results tuple into xst[par] on the main stream, the export stream copies
     // it to the caller's host block while the next kernels run
-    hipStream_t xstream = nullptr;
-    hipEvent_t ev_xready[2] = {nullptr, nullptr}, ev_xdone[2] = {nullptr, nullptr};
-    bool xdone_rec[2] = {false, false};             // ev_xdone[par] recorded (the staging may still be read)
-    DBuf xst[2];
-    int xpar = 0;
-    bool x_inflight = false;                        // copies queued on xstream
-    hipEvent_t ev_side[2] = {nullptr, nullptr};     // rays ready (main -> side), slivers done (side -> main)
+    struct Export {
+        Stream xstream;
+        Event ev_xready[2], ev_xdone[2];
+        bool xdone_rec[2] = {false, false};         // ev_xdone[par] recorded (the staging may still be read)
+        DBuf xst[2];
+        int xpar = 0;
+        bool x_inflight = false;                    // copies queued on xstream
+    } xp;
+    Event ev_side[2];                               // rays ready (main -> side), slivers done (side -> main)
     double host_last = 0.0;
     bool pop_init = false;                          // the population is I (the emitted rays, set_rays)
     bool mp_valid = false;                          // mp_last = the trace's measured power per measure mesh
@@ -255,19 +262,21 @@ struct lpc_handle {
     DBuf d_acc;
     DBuf d_tmp;                                     // misc small device scratch
     DBuf d_scan;                                    // RayScan of set_rays (k_ray_scan)
-    DBuf d_stats;                                   // walk counters (profiling)
-    DBuf d_fan;                                     // profiling: fan-triangle flags (SpillArgs::fan)
     DBuf d_mt, d_rng, d_etile;                      // device-born sources: generator state (key | pos), its
                                                     //   doubles, the fixed-order sums' tiles
-    // profiling
-    bool prof = false, prof_stats = false, prof_light = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_isect, ev_rest, ev_kern;
-    std::vector<hipEvent_t> ev_pool;
-    double prof_isect_ms = 0.0, prof_rest_ms = 0.0, prof_kern_ms = 0.0;
-    int64_t prof_launches = 0, prof_pairs = 0;
-    int prof_every = 1;                              // light mode: events on every prof_every-th walk launch
-    int64_t prof_seq = 0;                            // ... walk launches seen
-    bool prof_sampled = false;                       // the last run_queue's walk launch carries events
+    // profiling (lpc_prof_enable / lpc_prof_read)
+    struct Prof {
+        bool on = false, stats = false, light = false;
+        std::vector<std::pair<Event, Event>> ev_isect, ev_rest, ev_kern;   // recorded, not yet resolved
+        std::vector<Event> ev_pool;
+        double isect_ms = 0.0, rest_ms = 0.0, kern_ms = 0.0;
+        int64_t launches = 0, pairs = 0;
+        int every = 1;                              // light mode: events on every every-th walk launch
+        int64_t seq = 0;                            // ... walk launches seen
+        bool sampled = false;                       // the last run_queue's walk launch carries events
+        DBuf d_stats;                               // walk counters
+        DBuf d_fan;                                 // fan-triangle flags of the scene (SpillArgs::fan)
+    } prof;
     // ray-sharded trace (lpc_set_allreduce): the termination decisions and the
     // trace-end aggregates over all ranks
     lpc_allreduce_fn xchg = nullptr;
@@ -281,24 +290,32 @@ struct lpc_handle {
     struct RaySlot {
         Pop P;                                      // the batch as SoA rows (swapped with I when it is traced)
         DBuf aos;                                   // its (n,4) origin / direction rows (stage modes 0, 1)
-        void *pin = nullptr;                        // pinned host staging of the caller's rows
-        size_t pin_bytes = 0;
+        Pinned<void> pin;                           // pinned host staging of the caller's rows
         DBuf scan;                                  // k_ray_scan of the batch (device) ...
-        RayScan *scan_host = nullptr;               // ... and its pinned copy
-        hipEvent_t ev = nullptr;                    // the batch's copies, unpacks and scan done (cstream)
+        Pinned<RayScan> scan_host;                  // ... and its pinned copy
+        Event ev;                                   // the batch's copies, unpacks and scan done (cstream)
         std::thread th;
         int rc = 0;
         std::string err;
         int64_t n = 0;
         float max_ray_len = 1e3f, ior_env = 1.0f;
         int64_t scan_gen = -1;                      // the scene generation its scan keyed to (-1: none)
-    } rslot[2];
-    int64_t scene_gen = 0;                          // lpc_scene_upload count (the scan's key box)
-    int rs_head = 0, rs_count = 0;
-    hipStream_t cstream = nullptr;                  // copy stream of the staged batches
-    int stage_mode = 0;                             // LPC_STAGE_MODE: 0 pageable DMA (round 6 A/B: 1.23-1.28 G
+    };
+    struct Staged {
+        Stream cstream;                             // copy stream of the staged batches
+        Event ev_stage;                             // main-stream work before a stage call (cstream waits)
+        RaySlot rslot[2];
+        int rs_head = 0, rs_count = 0;
+        int stage_mode = 0;                         // LPC_STAGE_MODE: 0 pageable DMA (round 6 A/B: 1.23-1.28 G
                                                     //   fresh rays), 1 pinned rows (0.83-0.93), 2 pinned SoA chunks (0.77-1.0)
-    hipEvent_t ev_stage = nullptr;                  // main-stream work before a stage call (cstream waits)
+        void join()                                 // the helpers use the handle: they end before anything goes
+        {
+            for (auto &s : rslot)
+                if (s.th.joinable()) s.th.join();
+        }
+        ~Staged() { join(); }
+    } stage;
+    int64_t scene_gen = 0;                          // lpc_scene_upload count (the scan's key box)
 };
 
 static std::string g_open_err;
@@ -365,9 +382,9 @@ static int settle(lpc_handle *h)
         h->inflight = false;
         if (h->stream) HIPCHK(h, hipStreamSynchronize(h->stream));
     }
-    if (h && h->x_inflight) {                       // results-export copies to the caller's host blocks
-        h->x_inflight = false;
-        if (h->xstream) HIPCHK(h, hipStreamSynchronize(h->xstream));
+    if (h && h->xp.x_inflight) {                    // results-export copies to the caller's host blocks
+        h->xp.x_inflight = false;
+        if (h->xp.xstream) HIPCHK(h, hipStreamSynchronize(h->xp.xstream));
     }
     return 0;
 }
@@ -376,28 +393,19 @@ static int dalloc(lpc_handle *h, DBuf &b, size_t bytes, bool keep = false)
 {
     if (bytes == 0) bytes = 16;
     if (b.bytes >= bytes) return 0;
-    void *p = nullptr;
     // the stream may still use the old buffer (iterations return before their
     // last kernel ends): let it finish before the buffer goes
     if (b.p && h && h->stream) (void)hipStreamSynchronize(h->stream);
-    hipError_t e = hipMalloc(&p, bytes);
+    DBuf nb;
+    const hipError_t e = nb.alloc(bytes);
     if (e != hipSuccess)
-        return set_err(h, LPC_E_NOMEM, "hipMalloc(" + std::to_string(bytes) + " B): " + hipGetErrorString(e));
+        return set_err(h, LPC_E_NOMEM, "hipMalloc of " + std::to_string(bytes) + " B: " + hipGetErrorString(e));
     if (keep && b.p && b.bytes) {
-        HIPCHK(h, hipMemcpyAsync(p, b.p, b.bytes, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(nb.p, b.p, b.bytes, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
-    if (b.p) (void)hipFree(b.p);
-    b.p = p;
-    b.bytes = bytes;
+    b = std::move(nb);
     return 0;
-}
-
-static void dfree(DBuf &b)
-{
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
 }
 
 static int pop_reserve(lpc_handle *h, Pop &P, int64_t n)
@@ -405,7 +413,8 @@ static int pop_reserve(lpc_handle *h, Pop &P, int64_t n)
     if (P.cap >= n && P.buf.p) return 0;
     int64_t cap = std::max<int64_t>(n, 1024);
     if (P.buf.p && h->stream) (void)hipStreamSynchronize(h->stream);   // see dalloc
-    dfree(P.buf);
+    P.buf.reset();                      // the old rows are not kept: they go before the new block comes
+    P.cap = 0;
     RETIF(dalloc(h, P.buf, (size_t)cap * 8 * 4));
     P.cap = cap;
     return 0;
@@ -415,16 +424,9 @@ static inline unsigned grid1(int64_t n, int bs = 256) { return (unsigned)((n + b
 
 // ---------------------------------------------------------------------------
 // scene records: lpc_build.hpp builds them on the host (runs on host threads)
-static void drop_piece_tables(lpc_handle *h)
-{
-    for (auto &kv : h->ptabs) { dfree(kv.second.pieces); dfree(kv.second.spieces); dfree(kv.second.groups); }
-    h->ptabs.clear();
-}
-
 static int host_threads();
 static void host_parts(int64_t n, int T, const std::function<void(int64_t, int64_t, int)> &fn);
 static void host_pool_run(int n, const std::function<void(int)> &fn);
-static void stage_drop(lpc_handle *h);
 
 // Per mesh run: an 8-wide sphere hierarchy over its triangles in a top-down
 // median-split order, every node's test node_record() of ALL triangles below it
@@ -436,7 +438,7 @@ static int host_vertices(lpc_handle *h);
 
 static int build_records(lpc_handle *h)
 {
-    drop_piece_tables(h);   // pieces index the records built here
+    h->ptabs.clear();       // pieces index the records built here
     if (!h->src_v[0]) RETIF(host_vertices(h));       // a rebuild after the upload: the rows from the device
     SceneBuildIn in;
     in.v0 = h->src_v[0]; in.v1 = h->src_v[1]; in.v2 = h->src_v[2];
@@ -704,15 +706,15 @@ static ShadeOutPtrs shade_ptrs(lpc_handle *h, bool extra)
     return o;
 }
 
-static hipEvent_t ev_get(lpc_handle *h)
+static Event ev_get(lpc_handle *h)
 {
-    if (!h->ev_pool.empty()) {
-        hipEvent_t e = h->ev_pool.back();
-        h->ev_pool.pop_back();
-        return e;
+    Event e;
+    if (!h->prof.ev_pool.empty()) {
+        e = std::move(h->prof.ev_pool.back());
+        h->prof.ev_pool.pop_back();
+    } else {
+        (void)e.create(kEvTimingFlags);             // empty on failure
     }
-    hipEvent_t e;
-    if (hipEventCreateWithFlags(&e, kEvTimingFlags) != hipSuccess) return nullptr;
     return e;
 }
 
@@ -721,20 +723,20 @@ static void prof_resolve(lpc_handle *h)
 {
     // pairs whose end has not happened yet (a speculative iteration still queued)
     // stay for a later call
-    auto drain = [&](std::vector<std::pair<hipEvent_t, hipEvent_t>> &v, double &acc) {
+    auto drain = [&](std::vector<std::pair<Event, Event>> &v, double &acc) {
         size_t keep = 0;
         for (auto &pr : v) {
-            if (hipEventQuery(pr.second) == hipErrorNotReady) { v[keep++] = pr; continue; }
+            if (hipEventQuery(pr.second) == hipErrorNotReady) { v[keep++] = std::move(pr); continue; }
             float ms = 0.0f;
             if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) acc += ms;
-            h->ev_pool.push_back(pr.first);
-            h->ev_pool.push_back(pr.second);
+            h->prof.ev_pool.push_back(std::move(pr.first));
+            h->prof.ev_pool.push_back(std::move(pr.second));
         }
         v.resize(keep);
     };
-    drain(h->ev_isect, h->prof_isect_ms);
-    drain(h->ev_kern, h->prof_kern_ms);
-    drain(h->ev_rest, h->prof_rest_ms);
+    drain(h->prof.ev_isect, h->prof.isect_ms);
+    drain(h->prof.ev_kern, h->prof.kern_ms);
+    drain(h->prof.ev_rest, h->prof.rest_ms);
 }
 
 // Device-sized launch of a population whose size the previous iteration left in
@@ -750,8 +752,8 @@ struct DevSize {
 static int spill_setup(lpc_handle *h, int64_t n, SpillArgs *SP)
 {
     *SP = SpillArgs{nullptr, nullptr, 0u, 0, 31, h->tm_cur, nullptr};
-    if (h->prof_stats) {                // diagnostic: the fan triangles (apex valence >= 32), built once
-        if (!h->d_fan.p) {
+    if (h->prof.stats) {                // diagnostic: the fan triangles (apex valence >= 32), built once
+        if (!h->prof.d_fan.p) {
             RETIF(host_vertices(h));
             std::map<std::array<uint32_t, 3>, int32_t> val;
             auto key = [&](const std::vector<float> &v, int32_t i) {
@@ -763,10 +765,10 @@ static int spill_setup(lpc_handle *h, int64_t n, SpillArgs *SP)
             std::vector<uint8_t> f((size_t)h->M, 0);
             for (int32_t i = 0; i < h->M; ++i)
                 f[(size_t)i] = val[key(h->hv0, i)] >= 32 || val[key(h->hv1, i)] >= 32 || val[key(h->hv2, i)] >= 32;
-            RETIF(dalloc(h, h->d_fan, (size_t)h->M));
-            HIPCHK(h, hipMemcpy(h->d_fan.p, f.data(), (size_t)h->M, hipMemcpyHostToDevice));
+            RETIF(dalloc(h, h->prof.d_fan, (size_t)h->M));
+            HIPCHK(h, hipMemcpy(h->prof.d_fan.p, f.data(), (size_t)h->M, hipMemcpyHostToDevice));
         }
-        SP->fan = (const uint8_t *)h->d_fan.p;
+        SP->fan = (const uint8_t *)h->prof.d_fan.p;
     }
     if (h->spill_budget <= 0) return 0;
     RETIF(dalloc(h, h->w_spill, (size_t)2 * h->spill_cap * sizeof(SpillItem)));
@@ -978,11 +980,11 @@ static int run_queue(lpc_handle *h, const RaysIn &in, const float *rs, int64_t n
     const unsigned grid = (unsigned)h->walk_grid;      // single-wave blocks
     // profiling: the launch's own start/stop timestamps (hipExtLaunchKernel), no
     // event packets between the kernels
-    hipEvent_t k0 = nullptr, k1 = nullptr;
+    Event k0, k1;
     // light mode samples every prof_every-th launch: a launch with events costs
     // ~7 us more (bench A/B)
-    h->prof_sampled = h->prof && (!h->prof_light || h->prof_seq++ % h->prof_every == 0);
-    if (h->prof_sampled) { k0 = ev_get(h); k1 = ev_get(h); }
+    h->prof.sampled = h->prof.on && (!h->prof.light || h->prof.seq++ % h->prof.every == 0);
+    if (h->prof.sampled) { k0 = ev_get(h); k1 = ev_get(h); }
     // profiling counters only in the PROF instantiation, the merged sliver units
     // only in the MERGED one (fewer live registers without: the plain walk holds
     // 7 waves per SIMD, the merged one 6)
@@ -999,7 +1001,7 @@ static int run_queue(lpc_handle *h, const RaysIn &in, const float *rs, int64_t n
         LPC_LAUNCH_WALK(false, false);
     }
 #undef LPC_LAUNCH_WALK
-    if (h->prof_sampled) h->ev_kern.push_back({k0, k1});
+    if (h->prof.sampled) h->prof.ev_kern.emplace_back(std::move(k0), std::move(k1));
     RETIF(run_spill_levels(h, in, rs, n, perm, eps, max_ray_len, skey, scnt, stats, SP, ds ? ds->nd : nullptr));
     if (h->host_prof >= 2) {                          // diagnostic: this launch's hand-over queue lengths
         uint32_t q[8] = {0};
@@ -1026,15 +1028,11 @@ static bool side_stream(lpc_handle *h)
 {
     if (!h->side_tried) {
         h->side_tried = true;
-        const unsigned evf = hipEventDisableTiming;
-        if (hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&h->ev_side[0], evf) != hipSuccess ||
-            hipEventCreateWithFlags(&h->ev_side[1], evf) != hipSuccess) {
+        if (h->stream2.create() != hipSuccess || h->ev_side[0].create() != hipSuccess ||
+            h->ev_side[1].create() != hipSuccess) {
             (void)hipGetLastError();
-            if (h->stream2) (void)hipStreamDestroy(h->stream2);
-            for (hipEvent_t &e : h->ev_side)
-                if (e) { (void)hipEventDestroy(e); e = nullptr; }
-            h->stream2 = nullptr;
+            h->stream2.reset();
+            for (Event &e : h->ev_side) e.reset();
         }
     }
     return h->stream2 && h->ev_side[0] && h->ev_side[1];
@@ -1198,7 +1196,7 @@ static int run_intersect(lpc_handle *h, const RaysIn &in, int64_t n, float max_r
         }
         perm = nullptr;
     }
-    unsigned long long *stats = h->prof_stats ? (unsigned long long *)h->d_stats.p : nullptr;
+    unsigned long long *stats = h->prof.stats ? (unsigned long long *)h->prof.d_stats.p : nullptr;
     // sliver pieces the launch's rays can reach: dmin <= max |D| (sliver_dmin)
     if (!(dmax2 >= 0.0)) dmax2 = INFINITY;          // NaN bound (a NaN direction): no culling
     const float dmax = (float)std::min<double>(sqrt(dmax2 * (1.0 + 1e-5)), (double)INFINITY);
@@ -1247,22 +1245,22 @@ static int run_intersect(lpc_handle *h, const RaysIn &in, int64_t n, float max_r
         return 0;
     };
     if (!side && !merge_try) RETIF(launch_slivers());       // no side stream: before the walk, this stream
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->prof && !h->prof_light) { e0 = ev_get(h); e1 = ev_get(h); (void)hipEventRecord(e0, h->stream); }
-    h->prof_sampled = false;
+    Event e0, e1;
+    if (h->prof.on && !h->prof.light) { e0 = ev_get(h); e1 = ev_get(h); (void)hipEventRecord(e0, h->stream); }
+    h->prof.sampled = false;
     if (pt->npieces > 0) {
         const SliverArgs SAm = sliver_args(kSliverMergePpw);
         RETIF(run_queue(h, in, rs, n, perm, pt, eps, max_ray_len, skey, scnt, stats, ds, merge_try ? &SAm : nullptr,
                         roots_done));
     }
-    if (h->prof) {      // the intersect stage: the walk (+ k_packet, k_slivers)
-        if (!h->prof_light) {
+    if (h->prof.on) {      // the intersect stage: the walk (+ k_packet, k_slivers)
+        if (!h->prof.light) {
             (void)hipEventRecord(e1, h->stream);
-            h->ev_isect.push_back({e0, e1});
+            h->prof.ev_isect.emplace_back(std::move(e0), std::move(e1));
         }
-        if (!h->prof_light || h->prof_sampled) {
-            h->prof_launches += 1;
-            h->prof_pairs += n * (int64_t)h->M;
+        if (!h->prof.light || h->prof.sampled) {
+            h->prof.launches += 1;
+            h->prof.pairs += n * (int64_t)h->M;
         }
     }
     if (side) RETIF(launch_slivers());
@@ -1352,31 +1350,26 @@ int lpc_open(int device, lpc_handle **out)
         return set_err(nullptr, LPC_E_HIP, std::string("no HIP device: ") + hipGetErrorString(e));
     if (device < 0 || device >= c)
         return set_err(nullptr, LPC_E_ARG, "device ordinal " + std::to_string(device) + " out of range");
-    lpc_handle *h = new lpc_handle();
+    struct Closer { void operator()(lpc_handle *p) const { (void)lpc_close(p); } };
+    std::unique_ptr<lpc_handle, Closer> owner(new lpc_handle());    // closed on every failure below
+    lpc_handle *h = owner.get();
+    auto fail = [&](int rc) { g_open_err = h->err; return rc; };  // the handle's message outlives it
     h->device = device;
     e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        delete h;
-        return set_err(nullptr, LPC_E_HIP, std::string("stream: ") + hipGetErrorString(e));
-    }
+    if (e == hipSuccess) e = h->stream.create();
+    if (e != hipSuccess) return set_err(nullptr, LPC_E_HIP, std::string("stream: ") + hipGetErrorString(e));
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) {
         snprintf(h->name, sizeof(h->name), "%s (%s)", prop.name, prop.gcnArchName);
         h->cus = prop.multiProcessorCount;
     }
     int rc = dalloc(h, h->d_acc, sizeof(DevAcc));
-    if (rc) { g_open_err = h->err; lpc_close(h); return rc; }
-    rc = dalloc(h, h->d_mrun, LPC_MP_MAX * sizeof(double));
-    if (rc) { g_open_err = h->err; lpc_close(h); return rc; }
-    rc = dalloc(h, h->d_ctl, sizeof(IterCtl));
-    if (rc) { g_open_err = h->err; lpc_close(h); return rc; }
+    if (!rc) rc = dalloc(h, h->d_mrun, LPC_MP_MAX * sizeof(double));
+    if (!rc) rc = dalloc(h, h->d_ctl, sizeof(IterCtl));
+    if (rc) return fail(rc);
     if (hipMemset(h->d_acc.p, 0, sizeof(DevAcc)) != hipSuccess ||   // counters start empty (qerr 0)
-        hipMemset(h->d_ctl.p, 0, sizeof(IterCtl)) != hipSuccess) {
-        g_open_err = "counter init";
-        lpc_close(h);
-        return LPC_E_HIP;
-    }
+        hipMemset(h->d_ctl.p, 0, sizeof(IterCtl)) != hipSuccess)
+        return set_err(nullptr, LPC_E_HIP, "counter init");
     // size switches and test hooks (results do not depend on them; DESIGN.md
     // section 5): the tests drive the re-sort, the merged sliver units, the work
     // hand-over and its queue overflow, chunked iterations and a filter-record
@@ -1396,20 +1389,17 @@ int lpc_open(int device, lpc_handle **out)
     h->spill_large_per_tri = env_int("LPC_LARGE_PER_TRI", h->spill_large_per_tri);
     h->spill_cap = std::max<int64_t>(env_int("LPC_SPILL_CAP", h->spill_cap), 64);
     h->host_prof = (int)env_int("LPC_HOSTPROF", 0);
-    h->stage_mode = (int)std::min<int64_t>(2, std::max<int64_t>(0, env_int("LPC_STAGE_MODE", h->stage_mode)));
-    if (hipHostMalloc((void **)&h->acc_map, kAccRing * sizeof(DevAcc), hipHostMallocMapped | hipHostMallocCoherent) !=
-            hipSuccess ||
+    h->stage.stage_mode =
+        (int)std::min<int64_t>(2, std::max<int64_t>(0, env_int("LPC_STAGE_MODE", h->stage.stage_mode)));
+    if (h->acc_map.alloc(kAccRing * sizeof(DevAcc), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
         hipHostGetDevicePointer((void **)&h->acc_map_dev, h->acc_map, 0) != hipSuccess) {
-        h->acc_map = h->acc_map_dev = nullptr;       // counters then come by copy + stream sync
+        h->acc_map.reset();                          // counters then come by copy + stream sync
+        h->acc_map_dev = nullptr;
     } else {
         memset(h->acc_map, 0, kAccRing * sizeof(DevAcc));
     }
-    if (hipHostMalloc((void **)&h->acc_host, sizeof(DevAcc), hipHostMallocDefault) != hipSuccess) {
-        g_open_err = "pinned host buffer";
-        lpc_close(h);
-        return LPC_E_HIP;
-    }
-    *out = h;
+    if (h->acc_host.alloc(sizeof(DevAcc)) != hipSuccess) return set_err(nullptr, LPC_E_HIP, "pinned host buffer");
+    *out = owner.release();
     return 0;
 }
 
@@ -1418,41 +1408,20 @@ int lpc_close(lpc_handle *h)
     if (!h) return 0;
     (void)settle(h);                     // a trace still running (lpc_trace_iterate / _run_async)
     (void)hipSetDevice(h->device);
-    stage_drop(h);
-    for (auto &rs : h->rslot) {
-        dfree(rs.P.buf); dfree(rs.aos); dfree(rs.scan);
-        if (rs.pin) (void)hipHostFree(rs.pin);
-        if (rs.scan_host) (void)hipHostFree(rs.scan_host);
-        if (rs.ev) (void)hipEventDestroy(rs.ev);
-    }
-    if (h->ev_stage) (void)hipEventDestroy(h->ev_stage);
-    if (h->cstream) (void)hipStreamDestroy(h->cstream);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    DBuf *bufs[] = {&h->d_raw, &h->d_nodes, &h->w_pk, &h->d_xrec, &h->d_verts, &h->d_mat, &h->d_ior, &h->d_refl,
-                    &h->d_diss, &h->w_key, &h->w_sc, &h->w_rs, &h->d_live,
-                    &h->w_shf, &h->w_shi, &h->w_blk_cnt, &h->w_blk_off, &h->w_blk_pow, &h->w_soa,
-                    &h->w_stage, &h->w_sort, &h->w_sort_tmp, &h->w_bhist, &h->d_srec, &h->A.buf, &h->B.buf, &h->T.buf, &h->I.buf, &h->m_buf,
-                    &h->d_acc, &h->d_tmp, &h->d_scan, &h->d_stats, &h->d_misc, &h->w_spill, &h->w_qroots,
-                    &h->w_aos, &h->w_fc, &h->d_mrun, &h->w_gsum, &h->d_ctl, &h->d_cbase, &h->w_tbox, &h->d_pbox,
-                    &h->d_mt, &h->d_rng, &h->d_etile, &h->d_cull, &h->w_cull};
-    for (DBuf *b : bufs) dfree(*b);
-    if (h->acc_host) (void)hipHostFree(h->acc_host);
-    h->acc_host = nullptr;
-    if (h->acc_map) (void)hipHostFree(h->acc_map);
-    h->acc_map = h->acc_map_dev = nullptr;
-    for (auto &kv : h->ptabs) { dfree(kv.second.pieces); dfree(kv.second.spieces); dfree(kv.second.groups); }
-    prof_resolve(h);
-    for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
-    if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
-    if (h->xstream) { (void)hipStreamSynchronize(h->xstream); (void)hipStreamDestroy(h->xstream); }
-    for (int k = 0; k < 2; ++k) {
-        if (h->ev_xready[k]) (void)hipEventDestroy(h->ev_xready[k]);
-        if (h->ev_xdone[k]) (void)hipEventDestroy(h->ev_xdone[k]);
-        dfree(h->xst[k]);
-    }
-    for (hipEvent_t e : h->ev_side) if (e) (void)hipEventDestroy(e);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    h->stage.join();
+    // nothing is in flight when the members go (their owners release them, in
+    // reverse declaration order: see lpc_handle)
+    const hipStream_t streams[] = {h->stream, h->stream2, h->xp.xstream, h->stage.cstream};
+    for (hipStream_t s : streams)
+        if (s) (void)hipStreamSynchronize(s);
     delete h;
+    return 0;
+}
+
+int lpc_debug_live_bytes(int64_t *device_bytes, int64_t *pinned_bytes)
+{
+    if (device_bytes) *device_bytes = lpcr::g_device_bytes.load(std::memory_order_relaxed);
+    if (pinned_bytes) *pinned_bytes = lpcr::g_pinned_bytes.load(std::memory_order_relaxed);
     return 0;
 }
 
@@ -1492,7 +1461,7 @@ int lpc_scene_upload(lpc_handle *h, int32_t tri_count, const float *v0, const fl
         if (mesh_id[i] < 0 || mesh_id[i] >= K)
             return set_err(h, LPC_E_ARG, "mesh_id[" + std::to_string(i) + "] out of range");
     h->M = M; h->K = K;
-    dfree(h->d_fan);                                // profiling flags of the previous scene
+    h->prof.d_fan.reset();                          // profiling flags of the previous scene
     // the rows go to the device as they are (the vertex and exact records are
     // built there); the host reads the caller's arrays during this call and keeps
     // no copy (host_vertices fetches one for a later rebuild)
@@ -1791,9 +1760,7 @@ int lpc_bounce_host(lpc_handle *h, int64_t n, const float *origin4, const float 
         if (entering) d2h(entering + base, o.ent, (size_t)nc * 4);
         if (isect_idx) d2h(isect_idx + base, o.iidx, (size_t)nc * 4);
     }
-    dfree(P.buf);
-    dfree(dmeas);
-    if (h->prof) { (void)hipStreamSynchronize(h->stream); prof_resolve(h); }
+    if (h->prof.on) { (void)hipStreamSynchronize(h->stream); prof_resolve(h); }
     return rc;
 }
 
@@ -1826,7 +1793,7 @@ int lpc_intersect(lpc_handle *h, int64_t n, const float *dev_origin4, const floa
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     RETIF(check_qerr(h));
-    if (h->prof) prof_resolve(h);
+    if (h->prof.on) prof_resolve(h);
     return 0;
 }
 
@@ -2040,12 +2007,12 @@ static void stage_worker(lpc_handle *h, lpc_handle::RaySlot *s, const float *ori
     hipError_t e = hipSetDevice(h->device);
     if (e != hipSuccess) { fail(e, "hipSetDevice"); return; }
     const int64_t n = s->n;
-    hipStream_t cs = h->cstream;
-    const int mode = h->stage_mode;
+    hipStream_t cs = h->stage.cstream;
+    const int mode = h->stage.stage_mode;
     if (mode == 2) {
         // chunks: the host transposes chunk c + 1 into the pinned SoA arrays while
         // the DMAs of chunk c run (28 B per ray cross PCIe)
-        float *pin = (float *)s->pin;
+        float *pin = (float *)s->pin.p;
         const int64_t CH = (int64_t)1 << 18;
         const int T = std::max(1, std::min(4, host_threads()));
         for (int64_t lo = 0; lo < n; lo += CH) {
@@ -2072,7 +2039,7 @@ static void stage_worker(lpc_handle *h, lpc_handle::RaySlot *s, const float *ori
         float4 *so = (float4 *)s->aos.p, *sd = so + n;
         const char *src_o = (const char *)origin4, *src_d = (const char *)dir4, *src_p = (const char *)pow;
         if (mode == 1) {
-            char *pin = (char *)s->pin;
+            char *pin = (char *)s->pin.p;
             host_parts(n, host_threads(), [&](int64_t lo, int64_t hi, int) {
                 memcpy(pin + (size_t)lo * 16, origin4 + 4 * lo, (size_t)(hi - lo) * 16);
                 memcpy(pin + (size_t)n * 16 + (size_t)lo * 16, dir4 + 4 * lo, (size_t)(hi - lo) * 16);
@@ -2112,39 +2079,29 @@ static void stage_worker(lpc_handle *h, lpc_handle::RaySlot *s, const float *ori
     }
 }
 
-// Join the helpers and forget the staged batches (lpc_close).
-static void stage_drop(lpc_handle *h)
-{
-    for (auto &s : h->rslot)
-        if (s.th.joinable()) s.th.join();
-    h->rs_count = 0;
-    if (h->cstream) (void)hipStreamSynchronize(h->cstream);
-}
-
 int lpc_trace_stage_rays(lpc_handle *h, int64_t n, const float *origin4, const float *dir4, const float *pow,
                          float max_ray_len, float ior_env)
 {
     if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
     if (n <= 0 || !origin4 || !dir4 || !pow) return set_err(h, LPC_E_ARG, "stage_rays: need n > 0 rays and all buffers");
-    if (h->rs_count >= 2) return set_err(h, LPC_E_STATE, "stage_rays: two batches are staged already");
+    if (h->stage.rs_count >= 2) return set_err(h, LPC_E_STATE, "stage_rays: two batches are staged already");
     HIPCHK(h, hipSetDevice(h->device));
-    if (!h->cstream) {
-        HIPCHK(h, hipStreamCreateWithFlags(&h->cstream, hipStreamNonBlocking));
-        HIPCHK(h, hipEventCreateWithFlags(&h->ev_stage, hipEventDisableTiming));
+    if (!h->stage.cstream) {
+        HIPCHK(h, h->stage.cstream.create());
+        HIPCHK(h, h->stage.ev_stage.create());
     }
-    lpc_handle::RaySlot &s = h->rslot[(h->rs_head + h->rs_count) % 2];
+    lpc_handle::RaySlot &s = h->stage.rslot[(h->stage.rs_head + h->stage.rs_count) % 2];
     if (s.th.joinable()) s.th.join();
-    if (!s.ev) HIPCHK(h, hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-    if (!s.scan_host) HIPCHK(h, hipHostMalloc((void **)&s.scan_host, sizeof(RayScan), hipHostMallocDefault));
+    if (!s.ev) HIPCHK(h, s.ev.create());
+    if (!s.scan_host) HIPCHK(h, s.scan_host.alloc(sizeof(RayScan)));
     // buffers (allocations synchronise; they grow only with the batch size)
     RETIF(pop_reserve(h, s.P, n));
     RETIF(dalloc(h, s.scan, sizeof(RayScan)));
-    if (h->stage_mode != 2) RETIF(dalloc(h, s.aos, (size_t)n * 32));
-    const size_t pb = (size_t)n * (h->stage_mode == 2 ? 28 : 36);
-    if (h->stage_mode != 0 && s.pin_bytes < pb) {
-        if (s.pin) { (void)hipStreamSynchronize(h->cstream); (void)hipHostFree(s.pin); s.pin = nullptr; s.pin_bytes = 0; }
-        HIPCHK(h, hipHostMalloc(&s.pin, pb, hipHostMallocDefault));
-        s.pin_bytes = pb;
+    if (h->stage.stage_mode != 2) RETIF(dalloc(h, s.aos, (size_t)n * 32));
+    const size_t pb = (size_t)n * (h->stage.stage_mode == 2 ? 28 : 36);
+    if (h->stage.stage_mode != 0 && s.pin.bytes < pb) {
+        if (s.pin) (void)hipStreamSynchronize(h->stage.cstream);    // its last copies end before it goes
+        HIPCHK(h, s.pin.alloc(pb));
     }
     s.n = n;
     s.max_ray_len = max_ray_len;
@@ -2154,12 +2111,12 @@ int lpc_trace_stage_rays(lpc_handle *h, int64_t n, const float *origin4, const f
     s.scan_gen = h->M ? h->scene_gen : -1;      // no scene yet: the scan runs when the batch is traced
     // the slot's device buffers may hold an earlier batch's emitted rays: the copy
     // stream starts after the main-stream work queued so far
-    HIPCHK(h, hipEventRecord(h->ev_stage, h->stream));
-    HIPCHK(h, hipStreamWaitEvent(h->cstream, h->ev_stage, 0));
+    HIPCHK(h, hipEventRecord(h->stage.ev_stage, h->stream));
+    HIPCHK(h, hipStreamWaitEvent(h->stage.cstream, h->stage.ev_stage, 0));
     const float lo[3] = {h->box_lo[0], h->box_lo[1], h->box_lo[2]};
     const float sc[3] = {h->box_scale[0], h->box_scale[1], h->box_scale[2]};
     s.th = std::thread(stage_worker, h, &s, origin4, dir4, pow, lo, sc, s.scan_gen >= 0);
-    ++h->rs_count;
+    ++h->stage.rs_count;
     return 0;
 }
 
@@ -2171,16 +2128,16 @@ int lpc_trace_run_staged_async(lpc_handle *h, int32_t max_iter, double power_thr
                                int32_t *n_iter, int64_t *measured_count, double *mesh_power, int32_t mesh_power_cap)
 {
     if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
-    if (!h->rs_count) return set_err(h, LPC_E_STATE, "run_staged: no batch staged (lpc_trace_stage_rays)");
+    if (!h->stage.rs_count) return set_err(h, LPC_E_STATE, "run_staged: no batch staged (lpc_trace_stage_rays)");
     if (!h->M) return set_err(h, LPC_E_STATE, "no scene uploaded");
     if (mesh_power && mesh_power_cap < h->K)
         return set_err(h, LPC_E_ARG, "trace: mesh_power capacity below the scene's mesh count");
     if (!n_iter || (max_iter > 0 && !per_iter)) return set_err(h, LPC_E_ARG, "trace_run: null output");
     HIPCHK(h, hipSetDevice(h->device));
-    lpc_handle::RaySlot &s = h->rslot[h->rs_head];
+    lpc_handle::RaySlot &s = h->stage.rslot[h->stage.rs_head];
     if (s.th.joinable()) s.th.join();
-    h->rs_head ^= 1;
-    --h->rs_count;
+    h->stage.rs_head ^= 1;
+    --h->stage.rs_count;
     if (s.rc) return set_err(h, s.rc, s.err);
     // the analysis is read on the host (the copy ran during the previous trace);
     // the trace's first kernels wait for the batch on the device
@@ -2385,8 +2342,7 @@ static int ensure_measured(lpc_handle *h, int64_t need)
                                      (size_t)h->m_cap * 4, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
-    dfree(h->m_buf);
-    h->m_buf = nb;
+    h->m_buf = std::move(nb);
     h->m_cap = cap;
     return 0;
 }
@@ -2449,30 +2405,30 @@ struct ExportSpec {
 static int export_chunk(lpc_handle *h, const RaysIn &in, const ShadeOutPtrs &o, int64_t nc, int64_t base,
                         int64_t N, const ExportSpec &X)
 {
-    if (!h->xstream) {
-        HIPCHK(h, hipStreamCreateWithFlags(&h->xstream, hipStreamNonBlocking));
+    if (!h->xp.xstream) {
+        HIPCHK(h, h->xp.xstream.create());
         for (int k = 0; k < 2; ++k) {
-            HIPCHK(h, hipEventCreateWithFlags(&h->ev_xready[k], hipEventDisableTiming));
-            HIPCHK(h, hipEventCreateWithFlags(&h->ev_xdone[k], hipEventDisableTiming));
+            HIPCHK(h, h->xp.ev_xready[k].create());
+            HIPCHK(h, h->xp.ev_xdone[k].create());
         }
     }
-    const int par = h->xpar;
-    h->xpar ^= 1;
+    const int par = h->xp.xpar;
+    h->xp.xpar ^= 1;
     const size_t orow = X.org ? 16 : 0;
     const size_t row = orow + 16 + 4 + 4;
-    if (h->xst[par].bytes < (size_t)nc * row && h->xdone_rec[par])
-        HIPCHK(h, hipEventSynchronize(h->ev_xdone[par]));      // its last copy ends before it is freed
-    RETIF(dalloc(h, h->xst[par], (size_t)nc * row));
-    if (h->xdone_rec[par]) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_xdone[par], 0));
-    char *d = (char *)h->xst[par].p;
+    if (h->xp.xst[par].bytes < (size_t)nc * row && h->xp.xdone_rec[par])
+        HIPCHK(h, hipEventSynchronize(h->xp.ev_xdone[par]));   // its last copy ends before it is freed
+    RETIF(dalloc(h, h->xp.xst[par], (size_t)nc * row));
+    if (h->xp.xdone_rec[par]) HIPCHK(h, hipStreamWaitEvent(h->stream, h->xp.ev_xdone[par], 0));
+    char *d = (char *)h->xp.xst[par].p;
     float4 *xo = (float4 *)d;
     float4 *xd = (float4 *)(d + (size_t)nc * orow);
     float *xp = (float *)(d + (size_t)nc * (orow + 16));
     int32_t *xm = (int32_t *)(d + (size_t)nc * (orow + 20));
     hipLaunchKernelGGL(k_export, dim3(grid1(nc)), dim3(256), 0, h->stream, nc, in, o, X.org, xo, xd, xp, xm);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev_xready[par], h->stream));
-    HIPCHK(h, hipStreamWaitEvent(h->xstream, h->ev_xready[par], 0));
+    HIPCHK(h, hipEventRecord(h->xp.ev_xready[par], h->stream));
+    HIPCHK(h, hipStreamWaitEvent(h->xp.xstream, h->xp.ev_xready[par], 0));
     const double hm = h->host_prof ? host_us() : 0.0;
     // the copy into the caller's pinned block: a copy kernel writing the mapped
     // block over PCIe (round 5: hipMemcpyAsync into a block stalled the host 4-15 ms
@@ -2481,11 +2437,11 @@ static int export_chunk(lpc_handle *h, const RaysIn &in, const ShadeOutPtrs &o, 
     auto copy_out = [&](char *host, const char *dev, size_t bytes) -> int {
         void *hdev = nullptr;
         if (hipHostGetDevicePointer(&hdev, host, 0) == hipSuccess && hdev && (((uintptr_t)hdev | (uintptr_t)dev) & 15u) == 0) {
-            hipLaunchKernelGGL(k_copy_host, dim3(1024), dim3(256), 0, h->xstream, (const lpc_u4 *)dev, (lpc_u4 *)hdev,
+            hipLaunchKernelGGL(k_copy_host, dim3(1024), dim3(256), 0, h->xp.xstream, (const lpc_u4 *)dev, (lpc_u4 *)hdev,
                                (int64_t)(bytes / 16), (int64_t)bytes);
             HIPCHK(h, hipGetLastError());
         } else {
-            HIPCHK(h, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, h->xstream));
+            HIPCHK(h, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, h->xp.xstream));
         }
         return 0;
     };
@@ -2504,9 +2460,9 @@ static int export_chunk(lpc_handle *h, const RaysIn &in, const ShadeOutPtrs &o, 
             doff += (size_t)nc * elt[k];
         }
     }
-    HIPCHK(h, hipEventRecord(h->ev_xdone[par], h->xstream));
-    h->xdone_rec[par] = true;
-    h->x_inflight = true;
+    HIPCHK(h, hipEventRecord(h->xp.ev_xdone[par], h->xp.xstream));
+    h->xp.xdone_rec[par] = true;
+    h->xp.x_inflight = true;
     return 0;
 }
 
@@ -2576,7 +2532,7 @@ static int iter_enqueue(lpc_handle *h, float *out_origin4, float *out_dest4, flo
     // the counters come back through the mapped host ring k_scan / k_stage_move
     // write, so the host decides and launches the next iteration while the rows
     // still move (profiling: only the light level, whose events end before)
-    const bool early = h->acc_map_dev && (C >= N || traced) && !out_next_pow && (!h->prof || h->prof_light);
+    const bool early = h->acc_map_dev && (C >= N || traced) && !out_next_pow && (!h->prof.on || h->prof.light);
     ++h->acc_seq;
     P->seq = h->acc_seq;
     P->early = early;
@@ -2603,8 +2559,8 @@ static int iter_enqueue(lpc_handle *h, float *out_origin4, float *out_dest4, flo
         h->in_trace = false;
         RETIF(rc_i);
         if (traced) in = tin;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (h->prof && !h->prof_light) { e0 = ev_get(h); e1 = ev_get(h); (void)hipEventRecord(e0, h->stream); }
+        Event e0, e1;
+        if (h->prof.on && !h->prof.light) { e0 = ev_get(h); e1 = ev_get(h); (void)hipEventRecord(e0, h->stream); }
         ShadeOutPtrs o = shade_ptrs(h, false);
         CompactArgs A;
         A.n = nc; A.nb = (nc + 1023) / 1024; A.o = o;
@@ -2705,7 +2661,10 @@ static int iter_enqueue(lpc_handle *h, float *out_origin4, float *out_dest4, flo
             h->slots_mrl = h->max_ray_len;
             h->misc_clean = true;               // k_stage_move reset the next launch's words
             HIPCHK(h, hipGetLastError());
-            if (h->prof && !h->prof_light) { (void)hipEventRecord(e1, h->stream); h->ev_rest.push_back({e0, e1}); }
+            if (h->prof.on && !h->prof.light) {
+                (void)hipEventRecord(e1, h->stream);
+                h->prof.ev_rest.emplace_back(std::move(e0), std::move(e1));
+            }
             continue;
         }
         RETIF(run_shade(h, in, nullptr, nc, h->max_ray_len, h->ior_env, false));
@@ -2740,7 +2699,10 @@ static int iter_enqueue(lpc_handle *h, float *out_origin4, float *out_dest4, flo
         if (cut) hipLaunchKernelGGL(k_scatter<true>, dim3((unsigned)A.nb), dim3(256), 0, h->stream, A);
         else hipLaunchKernelGGL(k_scatter<false>, dim3((unsigned)A.nb), dim3(256), 0, h->stream, A);
         HIPCHK(h, hipGetLastError());
-        if (h->prof && !h->prof_light) { (void)hipEventRecord(e1, h->stream); h->ev_rest.push_back({e0, e1}); }
+        if (h->prof.on && !h->prof.light) {
+            (void)hipEventRecord(e1, h->stream);
+            h->prof.ev_rest.emplace_back(std::move(e0), std::move(e1));
+        }
     }
     // refracted block after the reflected one (k_append reads the counts on the
     // device), then the counters to the pinned copy: one host sync per iteration
@@ -2792,7 +2754,7 @@ static int iter_collect(lpc_handle *h, const Pending &P, float *out_next_pow, lp
         HIPCHK(h, hipMemcpyAsync(out_next_pow, h->A.f(6), (size_t)(nR + nT) * 4, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
-    if (h->prof) prof_resolve(h);
+    if (h->prof.on) prof_resolve(h);
     h->n_cur = nR + nT;
     h->m_total = (int64_t)acc.m_total;
     // the running per-mesh measured power stays valid while every iteration sums it
@@ -2912,7 +2874,7 @@ int lpc_host_seq_sum_f32(const float *x, int64_t n, float *out)
 // and the host drops the iteration when the ranks' sums end the trace.
 static bool ds_ok(const lpc_handle *h, int64_t bound)
 {
-    return h->spec && h->acc_map_dev && (!h->prof || h->prof_light) && bound > 0 && bound <= chunk_rays(h) &&
+    return h->spec && h->acc_map_dev && (!h->prof.on || h->prof.light) && bound > 0 && bound <= chunk_rays(h) &&
            bound < h->resort_min && (bound + 63) / 64 <= (int64_t)LPC_Q_MAX_PACKETS;
 }
 
@@ -3410,15 +3372,15 @@ int lpc_prof_enable(lpc_handle *h, int on)
 {
     if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
     RETIF(settle(h));                   // a trace still running (lpc_trace_iterate / _run_async)
-    h->prof_every = std::max(1, on >> 8);           // 4 + 256 k: light, every k-th walk launch
+    h->prof.every = std::max(1, on >> 8);           // 4 + 256 k: light, every k-th walk launch
     on &= 0xff;
-    h->prof_seq = 0;
-    h->prof = on != 0;
-    h->prof_stats = on == 2;
-    h->prof_light = on == 4;                        // k_rootwalk events only (bench timed region)
-    if (h->prof_stats && !h->d_stats.p) {
-        RETIF(dalloc(h, h->d_stats, LPC_STATS_WORDS * 8));
-        HIPCHK(h, hipMemset(h->d_stats.p, 0, LPC_STATS_WORDS * 8));
+    h->prof.seq = 0;
+    h->prof.on = on != 0;
+    h->prof.stats = on == 2;
+    h->prof.light = on == 4;                        // k_rootwalk events only (bench timed region)
+    if (h->prof.stats && !h->prof.d_stats.p) {
+        RETIF(dalloc(h, h->prof.d_stats, LPC_STATS_WORDS * 8));
+        HIPCHK(h, hipMemset(h->prof.d_stats.p, 0, LPC_STATS_WORDS * 8));
     }
     return 0;
 }
@@ -3429,15 +3391,15 @@ int lpc_prof_read(lpc_handle *h, lpc_prof *out, int reset)
     RETIF(settle(h));                   // a trace still running (lpc_trace_iterate / _run_async)
     (void)hipStreamSynchronize(h->stream);
     prof_resolve(h);
-    out->intersect_ms = h->prof_isect_ms;
-    out->kernel_ms = h->prof_kern_ms;
-    out->shade_ms = h->prof_rest_ms;
-    out->intersect_launches = h->prof_launches;
+    out->intersect_ms = h->prof.isect_ms;
+    out->kernel_ms = h->prof.kern_ms;
+    out->shade_ms = h->prof.rest_ms;
+    out->intersect_launches = h->prof.launches;
     out->xchg_us = h->xchg_us;
     out->xchg_calls = h->xchg_calls;
-    out->pairs = h->prof_pairs;
+    out->pairs = h->prof.pairs;
     std::vector<unsigned long long> st(LPC_STATS_WORDS, 0ull);
-    if (h->d_stats.p) HIPCHK(h, hipMemcpy(st.data(), h->d_stats.p, LPC_STATS_WORDS * 8, hipMemcpyDeviceToHost));
+    if (h->prof.d_stats.p) HIPCHK(h, hipMemcpy(st.data(), h->prof.d_stats.p, LPC_STATS_WORDS * 8, hipMemcpyDeviceToHost));
     out->node_visits = (int64_t)st[0];
     out->group_tests = (int64_t)st[1];
     out->wave_traversals = (int64_t)st[2];
@@ -3456,9 +3418,9 @@ int lpc_prof_read(lpc_handle *h, lpc_prof *out, int reset)
         if (v > out->heavy_piece_ticks) { out->heavy_piece_ticks = v; out->heavy_piece = p; }
     }
     if (reset) {
-        h->prof_isect_ms = h->prof_rest_ms = h->prof_kern_ms = 0.0; h->prof_launches = h->prof_pairs = 0;
+        h->prof.isect_ms = h->prof.rest_ms = h->prof.kern_ms = 0.0; h->prof.launches = h->prof.pairs = 0;
         h->xchg_us = 0.0; h->xchg_calls = 0;
-        if (h->d_stats.p) HIPCHK(h, hipMemset(h->d_stats.p, 0, LPC_STATS_WORDS * 8));
+        if (h->prof.d_stats.p) HIPCHK(h, hipMemset(h->prof.d_stats.p, 0, LPC_STATS_WORDS * 8));
     }
     return 0;
 }
@@ -3514,39 +3476,35 @@ int lpc_rng_mt19937(lpc_handle *h, uint32_t *key, int32_t *pos, int64_t n, doubl
 // wrote it recorded (a consumer on another stream waits on it).
 struct lpc_rays {
     int device = 0;
-    float4 *origin = nullptr, *dir = nullptr;
-    float *pow = nullptr;
+    DBuf origin_rows, dir_rows, pow_vals;
     int64_t n = 0;
     double power_sum = 0.0;
-    hipEvent_t ready = nullptr;
+    Event ready;
+    float4 *origin() const { return (float4 *)origin_rows.p; }
+    float4 *dir() const { return (float4 *)dir_rows.p; }
+    float *pow() const { return (float *)pow_vals.p; }
 };
 
 static void rays_destroy(lpc_rays *r)
 {
-    if (!r) return;
-    if (r->ready) { (void)hipEventSynchronize(r->ready); (void)hipEventDestroy(r->ready); }
-    if (r->origin) (void)hipFree(r->origin);
-    if (r->dir) (void)hipFree(r->dir);
-    if (r->pow) (void)hipFree(r->pow);
+    if (r && r->ready) (void)hipEventSynchronize(r->ready);    // its last writer ends before the rows go
     delete r;
 }
 
 static int rays_create(lpc_handle *h, int64_t n, lpc_rays **out)
 {
-    lpc_rays *r = new lpc_rays();
+    std::unique_ptr<lpc_rays> r(new lpc_rays());
     r->device = h->device;
     r->n = n;
     const size_t rows = (size_t)std::max<int64_t>(n, 1);
-    hipError_t e = hipMalloc((void **)&r->origin, rows * 16);
-    if (e == hipSuccess) e = hipMalloc((void **)&r->dir, rows * 16);
-    if (e == hipSuccess) e = hipMalloc((void **)&r->pow, rows * 4);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&r->ready, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        rays_destroy(r);
+    hipError_t e = r->origin_rows.alloc(rows * 16);
+    if (e == hipSuccess) e = r->dir_rows.alloc(rows * 16);
+    if (e == hipSuccess) e = r->pow_vals.alloc(rows * 4);
+    if (e == hipSuccess) e = r->ready.create();
+    if (e != hipSuccess)
         return set_err(h, LPC_E_NOMEM, std::string("device source of ") + std::to_string(n) + " rays: " +
                                            hipGetErrorString(e));
-    }
-    *out = r;
+    *out = r.release();
     return 0;
 }
 
@@ -3616,7 +3574,7 @@ int lpc_rays_emit_hemisphere(lpc_handle *h, uint32_t *key, int32_t *pos, int64_t
     A.m = m;
     lpc_rays *r = nullptr;
     RETIF(rays_create(h, count, &r));
-    A.origin = r->origin; A.dirs = r->dir; A.pow = r->pow;
+    A.origin = r->origin(); A.dirs = r->dir(); A.pow = r->pow();
     const int rc = emit_hemisphere(h, r, key, pos, A);
     if (rc) { rays_destroy(r); return rc; }
     *out = r;
@@ -3644,7 +3602,7 @@ int lpc_rays_emit_collimated(lpc_handle *h, uint32_t *key, int32_t *pos, int64_t
     A.diameter = diameter;
     lpc_rays *r = nullptr;
     RETIF(rays_create(h, count, &r));
-    A.origin = r->origin; A.dirs = r->dir; A.pow = r->pow;
+    A.origin = r->origin(); A.dirs = r->dir(); A.pow = r->pow();
     const int rc = emit_collimated(h, r, key, pos, A);
     if (rc) { rays_destroy(r); return rc; }
     *out = r;
@@ -3662,7 +3620,7 @@ int lpc_rays_rotate(lpc_handle *h, lpc_rays *r, const double *R9, const double *
         A.n = r->n;
         memcpy(A.R, R9, sizeof(A.R));
         memcpy(A.piv, pivot4, sizeof(A.piv));
-        A.origin = r->origin; A.dirs = r->dir;
+        A.origin = r->origin(); A.dirs = r->dir();
         HIPCHK(h, hipStreamWaitEvent(h->stream, r->ready, 0));
         hipLaunchKernelGGL(k_rays_rotate, dim3(grid1(r->n)), dim3(256), 0, h->stream, A);
         HIPCHK(h, hipGetLastError());
@@ -3686,9 +3644,9 @@ int lpc_rays_fetch(lpc_handle *h, const lpc_rays *r, float *origin4, float *dir4
     HIPCHK(h, hipSetDevice(r->device));
     HIPCHK(h, hipEventSynchronize(r->ready));
     if (r->n > 0) {
-        if (origin4) HIPCHK(h, hipMemcpy(origin4, r->origin, (size_t)r->n * 16, hipMemcpyDeviceToHost));
-        if (dir4) HIPCHK(h, hipMemcpy(dir4, r->dir, (size_t)r->n * 16, hipMemcpyDeviceToHost));
-        if (pow) HIPCHK(h, hipMemcpy(pow, r->pow, (size_t)r->n * 4, hipMemcpyDeviceToHost));
+        if (origin4) HIPCHK(h, hipMemcpy(origin4, r->origin(), (size_t)r->n * 16, hipMemcpyDeviceToHost));
+        if (dir4) HIPCHK(h, hipMemcpy(dir4, r->dir(), (size_t)r->n * 16, hipMemcpyDeviceToHost));
+        if (pow) HIPCHK(h, hipMemcpy(pow, r->pow(), (size_t)r->n * 4, hipMemcpyDeviceToHost));
     }
     HIPCHK(h, hipSetDevice(h->device));
     return 0;
@@ -3728,11 +3686,11 @@ int lpc_trace_set_rays_dev(lpc_handle *h, lpc_rays *const *list, int32_t count, 
             const lpc_rays *r = list[k];
             if (r->n == 0) continue;
             HIPCHK(h, hipStreamWaitEvent(h->stream, r->ready, 0));
-            hipLaunchKernelGGL(k_unpack4, dim3(grid1(r->n)), dim3(256), 0, h->stream, r->n, (const float4 *)r->origin,
+            hipLaunchKernelGGL(k_unpack4, dim3(grid1(r->n)), dim3(256), 0, h->stream, r->n, (const float4 *)r->origin(),
                                h->I.f(0) + off, h->I.f(1) + off, h->I.f(2) + off);
-            hipLaunchKernelGGL(k_unpack4, dim3(grid1(r->n)), dim3(256), 0, h->stream, r->n, (const float4 *)r->dir,
+            hipLaunchKernelGGL(k_unpack4, dim3(grid1(r->n)), dim3(256), 0, h->stream, r->n, (const float4 *)r->dir(),
                                h->I.f(3) + off, h->I.f(4) + off, h->I.f(5) + off);
-            HIPCHK(h, hipMemcpyAsync(h->I.f(6) + off, r->pow, (size_t)r->n * 4, hipMemcpyDeviceToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(h->I.f(6) + off, r->pow(), (size_t)r->n * 4, hipMemcpyDeviceToDevice, h->stream));
             off += r->n;
         }
         HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)h->I.pmid(), -2, (size_t)n, h->stream));
