@@ -27,6 +27,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace lpck;
@@ -48,20 +49,15 @@ struct Pop {
     int64_t cap = 0;
     float *f(int k) const { return (float *)buf.p + (size_t)k * cap; }
     int32_t *pmid() const { return (int32_t *)((float *)buf.p + (size_t)7 * cap); }
-    RaysIn in(int64_t off = 0) const {
-        RaysIn r;
+    template <class R> R rows(int64_t off) const {
+        R r;
         r.ox = f(0) + off; r.oy = f(1) + off; r.oz = f(2) + off;
         r.dx = f(3) + off; r.dy = f(4) + off; r.dz = f(5) + off;
         r.pw = f(6) + off; r.pmid = pmid() + off;
         return r;
     }
-    RaysOut out(int64_t off = 0) const {
-        RaysOut r;
-        r.ox = f(0) + off; r.oy = f(1) + off; r.oz = f(2) + off;
-        r.dx = f(3) + off; r.dy = f(4) + off; r.dz = f(5) + off;
-        r.pw = f(6) + off; r.pmid = pmid() + off;
-        return r;
-    }
+    RaysIn in(int64_t off = 0) const { return rows<RaysIn>(off); }
+    RaysOut out(int64_t off = 0) const { return rows<RaysOut>(off); }
 };
 
 struct PieceTable {
@@ -70,6 +66,17 @@ struct PieceTable {
     DBuf groups;                       // k_roots_s gate: the runs' root records, s_lo/s_hi = their pieces
     int32_t ngroups = 0;               // 0: no gate (pieces are the run roots, or > 64 runs)
     std::vector<float> sdmin;          // per sliver piece (ascending): min dmin of its slivers
+};
+
+// The trace's current population and its role: the one record of it.  An enqueued
+// iteration replaces it whole, a discarded one puts it back (Pending::before).
+struct PopState {
+    int64_t n = 0;              // rays (iter_collect: the kept children)
+    double dmax2 = INFINITY;    // their max |D|^2 (iter_collect)
+    bool init = false;          // the population is I (the emitted rays, set_rays), else A
+    bool traced = false;        // it is in its parents' traced order
+    bool emitted = false;       // it is the emitted rays (set_rays)
+    bool pbox_ok = false;       // d_pbox holds its origin box
 };
 
 const int kShadeF = 12;   // float arrays of the shade outputs
@@ -151,7 +158,7 @@ struct lpc_handle {
     std::vector<std::vector<int32_t>> run_levels;    // per run: (first node, count) per level, root first
     std::vector<FiltRec> node_self;                  // each node's own test (piece roots)
     std::vector<float> sliver_dmin_host;             // SliverRec::dmin, host copy
-    double pop_dmax2 = INFINITY, init_dmax2 = INFINITY;   // max |D|^2 of the trace population / emitted rays
+    double init_dmax2 = INFINITY;                    // max |D|^2 of the emitted rays
     std::vector<int32_t> run_slo, run_shi;           // sliver records per run
     int64_t n_slivers = 0;
     int64_t n_thin = 0;                              // of them thin triangles (thin_axis, k = 1)
@@ -188,22 +195,17 @@ struct lpc_handle {
     bool misc_clean = false;                        // the launch words were reset for the next launch
     int half = 3;                                   // LPC_HALF: 3 = half-line cull at the piece roots of chained
                                                     //   populations (run_intersect), 0 = off
-    bool half_roots = false;                        // ... at the piece roots (k_roots)
-    bool in_trace = false;                          // run_intersect called from lpc_trace_iterate
     DBuf d_live;                                    // [K] slot written by some run
     DBuf w_pk;                                      // PacketRec per 128-ray wave (k_slivers)
     DBuf d_misc;                                    // LPC_MISC_WORDS per-launch words
     size_t sort_tmp_bytes = 0;
     int64_t resort_min = 2000000;                   // chained traced populations from this size are sorted again
-    uint32_t *tm_cur = nullptr;                     // this launch's masks (the walk writes, k_shade_stage reads)
     // work hand-over (LPC_BUDGET, LPC_SPILL_CAP, LPC_LARGE_PER_TRI: tests drive the
     // queue-overflow and budget paths at small sizes)
     int spill_budget = 20;                          // node visits before a wave hands over (0 off)
     int64_t spill_large_per_tri = 16;
     int64_t spill_cap = (int64_t)1 << 22;           // k_spill queue capacity (items)
     DBuf w_spill;                                   // k_spill queue
-    bool pop_traced = false;                        // the population is in its parents' traced order
-    bool pop_emitted = false;                       // the population is the emitted rays (set_rays)
     int init_key_lo = 0, init_key_hi = 32;          // key bits that vary over the emitted rays (set_rays)
     bool init_bsort = false;                        // their sort may be the counting sort (bsort_fits)
     DBuf w_qroots;                                  // root items
@@ -238,12 +240,10 @@ struct lpc_handle {
     } xp;
     Event ev_side[2];                               // rays ready (main -> side), slivers done (side -> main)
     double host_last = 0.0;
-    bool pop_init = false;                          // the population is I (the emitted rays, set_rays)
     bool mp_valid = false;                          // mp_last = the trace's measured power per measure mesh
     DBuf d_mrun;                                    // its running sums on the device (k_stage_move)
     DBuf d_cbase;                                   // chunked traced iterations: running row bases (ping-pong)
     DBuf w_tbox, d_pbox;                            // per-tile boxes (k_shade_stage), the population's box (k_stage_move)
-    bool pbox_ok = false;                           // d_pbox holds the current population's origin box
     double mp_last[LPC_MP_MAX] = {0, 0, 0, 0};
     // per-ray power cutoff (lpc_trace_set_min_power) and its ledger (lpc_trace_culled)
     float min_power = 0.0f;                         // 0: off (the default instantiations of the compaction kernels)
@@ -253,7 +253,8 @@ struct lpc_handle {
     int64_t it_done = 0;                            // iterations collected since the trace's reset
     // trace
     Pop A, B, T, I;
-    int64_t n_cur = 0, n_init = 0;
+    PopState pop;                                   // which of them is current, and as what
+    int64_t n_init = 0;
     float max_ray_len = 1e3f, ior_env = 1.0f;
     bool traced_ready = false;
     bool inflight = false;                          // the stream may still run a trace's last kernels (settle)
@@ -273,7 +274,6 @@ struct lpc_handle {
         int64_t launches = 0, pairs = 0;
         int every = 1;                              // light mode: events on every every-th walk launch
         int64_t seq = 0;                            // ... walk launches seen
-        bool sampled = false;                       // the last run_queue's walk launch carries events
         DBuf d_stats;                               // walk counters
         DBuf d_fan;                                 // fan-triangle flags of the scene (SpillArgs::fan)
     } prof;
@@ -339,38 +339,27 @@ static int set_err(lpc_handle *h, int code, const std::string &msg)
         if (rc_) return rc_;      \
     } while (0)
 
-// Shading kernels templated on the register-resident slot count KU (shade_eval):
-// the smallest of 4, 8, 12, 16 that holds the scene's K meshes, 0 = slots read
-// from memory as postproc needs them (K > 16).
-#define LPC_KU_LAUNCH(h, KERN, grid, block, stream, ...)                                          \
-    do {                                                                                         \
-        const int K_ = (h)->K;                                                                   \
-        if (K_ <= 4) hipLaunchKernelGGL(KERN<4>, grid, block, 0, stream, __VA_ARGS__);           \
-        else if (K_ <= 8) hipLaunchKernelGGL(KERN<8>, grid, block, 0, stream, __VA_ARGS__);      \
-        else if (K_ <= 12) hipLaunchKernelGGL(KERN<12>, grid, block, 0, stream, __VA_ARGS__);    \
-        else if (K_ <= 16) hipLaunchKernelGGL(KERN<16>, grid, block, 0, stream, __VA_ARGS__);    \
-        else hipLaunchKernelGGL(KERN<0>, grid, block, 0, stream, __VA_ARGS__);                   \
-    } while (0)
+// Picking a kernel's instantiation from a run-time value: f is a generic lambda,
+// called with the value as a compile-time constant (decltype(x)::value).
+// with_ku: the shading kernels' register-resident slot count KU (shade_eval), the
+// smallest of 4, 8, 12, 16 that holds the scene's K meshes, 0 = slots read from
+// memory as postproc needs them (K > 16).
+template <class F>
+static void with_ku(int K, F &&f)
+{
+    if (K <= 4) f(std::integral_constant<int, 4>{});
+    else if (K <= 8) f(std::integral_constant<int, 8>{});
+    else if (K <= 12) f(std::integral_constant<int, 12>{});
+    else if (K <= 16) f(std::integral_constant<int, 16>{});
+    else f(std::integral_constant<int, 0>{});
+}
 
-#define LPC_KU_LAUNCH2(h, KERN, B, grid, block, stream, ...)                                      \
-    do {                                                                                         \
-        const int K_ = (h)->K;                                                                   \
-        if (K_ <= 4) hipLaunchKernelGGL((KERN<4, B>), grid, block, 0, stream, __VA_ARGS__);      \
-        else if (K_ <= 8) hipLaunchKernelGGL((KERN<8, B>), grid, block, 0, stream, __VA_ARGS__); \
-        else if (K_ <= 12) hipLaunchKernelGGL((KERN<12, B>), grid, block, 0, stream, __VA_ARGS__); \
-        else if (K_ <= 16) hipLaunchKernelGGL((KERN<16, B>), grid, block, 0, stream, __VA_ARGS__); \
-        else hipLaunchKernelGGL((KERN<0, B>), grid, block, 0, stream, __VA_ARGS__);              \
-    } while (0)
-
-#define LPC_KU_LAUNCH3(h, KERN, B, C, grid, block, stream, ...)                                      \
-    do {                                                                                            \
-        const int K_ = (h)->K;                                                                      \
-        if (K_ <= 4) hipLaunchKernelGGL((KERN<4, B, C>), grid, block, 0, stream, __VA_ARGS__);      \
-        else if (K_ <= 8) hipLaunchKernelGGL((KERN<8, B, C>), grid, block, 0, stream, __VA_ARGS__); \
-        else if (K_ <= 12) hipLaunchKernelGGL((KERN<12, B, C>), grid, block, 0, stream, __VA_ARGS__); \
-        else if (K_ <= 16) hipLaunchKernelGGL((KERN<16, B, C>), grid, block, 0, stream, __VA_ARGS__); \
-        else hipLaunchKernelGGL((KERN<0, B, C>), grid, block, 0, stream, __VA_ARGS__);              \
-    } while (0)
+template <class F>
+static void with_bool(bool b, F &&f)
+{
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
 
 // Wait for a trace's kernels still queued on the stream: lpc_trace_iterate and
 // lpc_trace_run_async return once the iteration counters are published, while
@@ -748,10 +737,11 @@ struct DevSize {
     int64_t bound;              // capacity bound: workspaces, root-item shards
 };
 
-// Work hand-over (k_spill levels): queue, budget by population size.
-static int spill_setup(lpc_handle *h, int64_t n, SpillArgs *SP)
+// Work hand-over (k_spill levels): queue, budget by population size.  tmask:
+// the launch's written-slot masks (run_intersect), or NULL.
+static int spill_setup(lpc_handle *h, int64_t n, uint32_t *tmask, SpillArgs *SP)
 {
-    *SP = SpillArgs{nullptr, nullptr, 0u, 0, 31, h->tm_cur, nullptr};
+    *SP = SpillArgs{nullptr, nullptr, 0u, 0, 31, tmask, nullptr};
     if (h->prof.stats) {                // diagnostic: the fan triangles (apex valence >= 32), built once
         if (!h->prof.d_fan.p) {
             RETIF(host_vertices(h));
@@ -820,7 +810,6 @@ static int run_spill_levels(lpc_handle *h, const RaysIn &in, const float *rs, in
                             float eps, float max_ray_len, unsigned long long *skey, int32_t *scnt,
                             unsigned long long *stats, const SpillArgs &SP, const long long *nd = nullptr)
 {
-    uint32_t *misc = (uint32_t *)h->d_misc.p;
     RayBase ray;
     RETIF(ray_base(h, in, rs, n, &ray));
     const int levels = spill_level_count(h, n, SP);
@@ -831,14 +820,11 @@ static int run_spill_levels(lpc_handle *h, const RaysIn &in, const float *rs, in
         // 4-wave units, launched as single-wave blocks
         const unsigned g = (unsigned)std::max<int64_t>(kSpillMinBlocks, kSpillBlocks >> l) * 4u;
         // profiling counters only in the PROF instantiation (fewer live registers without)
-        if (stats)
-            hipLaunchKernelGGL((k_spill<8, true>), dim3(g), dim3(64), 0, h->stream, ray, n, perm,
+        with_bool(stats != nullptr, [&](auto pf) {
+            hipLaunchKernelGGL((k_spill<8, decltype(pf)::value>), dim3(g), dim3(64), 0, h->stream, ray, n, perm,
                                (const Node8 *)h->d_nodes.p, (const ExactRec *)h->d_xrec.p, eps, max_ray_len, skey,
                                scnt, stats, I, O, nd);
-        else
-            hipLaunchKernelGGL((k_spill<8, false>), dim3(g), dim3(64), 0, h->stream, ray, n, perm,
-                               (const Node8 *)h->d_nodes.p, (const ExactRec *)h->d_xrec.p, eps, max_ray_len, skey,
-                               scnt, stats, I, O, nd);
+        });
     }
     HIPCHK(h, hipGetLastError());
     return 0;
@@ -937,12 +923,14 @@ static int queue_args(lpc_handle *h, int64_t n, const PieceTable *pt, const DevS
 
 // The hierarchy stage: k_roots_s writes the (packet, piece) items whose root test
 // passes, k_rootwalk walks them grid-stride and hands heavy subtrees to the
-// k_spill levels.  roots_done: k_gather_roots already wrote
-// the items (same queue arguments).
+// k_spill levels.  half: the half-line cull at the piece
+// roots; tmask: the launch's written-slot masks or NULL (both run_intersect's).
+// roots_done: k_gather_roots already wrote the items (same queue arguments).
+// *sampled: the walk launch carries profiling events.
 static int run_queue(lpc_handle *h, const RaysIn &in, const float *rs, int64_t n, const int32_t *perm,
                      const PieceTable *pt, float eps, float max_ray_len, unsigned long long *skey, int32_t *scnt,
-                     unsigned long long *stats, const DevSize *ds = nullptr, const SliverArgs *merged = nullptr,
-                     bool roots_done = false)
+                     unsigned long long *stats, const DevSize *ds, const SliverArgs *merged, bool roots_done,
+                     bool half, uint32_t *tmask, bool *sampled)
 {
     QueueArgs Q;
     QueueShape sh;
@@ -956,12 +944,10 @@ static int run_queue(lpc_handle *h, const RaysIn &in, const float *rs, int64_t n
         const RootsBatch b = roots_batch(sh.npk, ds, np);
         const Piece *pc = (const Piece *)pt->pieces.p + (size_t)k * LPC_ROOTS_BATCH;
         const dim3 rg((unsigned)std::max<int64_t>(b.blocks, 1));
-        if (h->half_roots)
-            hipLaunchKernelGGL(k_roots_s<true>, rg, dim3(256), 0, h->stream, in, rs, n, pc, (int)np,
+        with_bool(half, [&](auto hf) {
+            hipLaunchKernelGGL(k_roots_s<decltype(hf)::value>, rg, dim3(256), 0, h->stream, in, rs, n, pc, (int)np,
                                (const Piece *)pt->groups.p, (int)pt->ngroups, Q, b.S, b.pb, ds ? ds->nd : nullptr);
-        else
-            hipLaunchKernelGGL(k_roots_s<false>, rg, dim3(256), 0, h->stream, in, rs, n, pc, (int)np,
-                               (const Piece *)pt->groups.p, (int)pt->ngroups, Q, b.S, b.pb, ds ? ds->nd : nullptr);
+        });
     }
     // merged sliver tests (LPC_SLIVER_MERGE): the packet bounds before the walk,
     // on this stream; the walk's waves take the (packet group, piece) units
@@ -976,32 +962,27 @@ static int run_queue(lpc_handle *h, const RaysIn &in, const float *rs, int64_t n
     RayBase ray;
     RETIF(ray_base(h, in, rs, n, &ray));
     SpillArgs SP;
-    RETIF(spill_setup(h, n, &SP));
+    RETIF(spill_setup(h, n, tmask, &SP));
     const unsigned grid = (unsigned)h->walk_grid;      // single-wave blocks
     // profiling: the launch's own start/stop timestamps (hipExtLaunchKernel), no
     // event packets between the kernels
     Event k0, k1;
     // light mode samples every prof_every-th launch: a launch with events costs
     // ~7 us more (bench A/B)
-    h->prof.sampled = h->prof.on && (!h->prof.light || h->prof.seq++ % h->prof.every == 0);
-    if (h->prof.sampled) { k0 = ev_get(h); k1 = ev_get(h); }
+    *sampled = h->prof.on && (!h->prof.light || h->prof.seq++ % h->prof.every == 0);
+    if (*sampled) { k0 = ev_get(h); k1 = ev_get(h); }
     // profiling counters only in the PROF instantiation, the merged sliver units
     // only in the MERGED one (fewer live registers without: the plain walk holds
     // 7 waves per SIMD, the merged one 6)
-#define LPC_LAUNCH_WALK(PF, MG)                                                                                     \
-    hipExtLaunchKernelGGL((k_rootwalk<8, PF, MG>), dim3(grid), dim3(64), 0, h->stream, k0, k1, 0, ray, n, perm,      \
-                          (const Node8 *)h->d_nodes.p, (const ExactRec *)h->d_xrec.p, eps, max_ray_len, skey, scnt, \
-                          stats, Q, SP, ds ? ds->nd : nullptr, SA)
-    if (stats) {
-        if (merged) LPC_LAUNCH_WALK(true, true);
-        else LPC_LAUNCH_WALK(true, false);
-    } else if (merged) {
-        LPC_LAUNCH_WALK(false, true);
-    } else {
-        LPC_LAUNCH_WALK(false, false);
-    }
-#undef LPC_LAUNCH_WALK
-    if (h->prof.sampled) h->prof.ev_kern.emplace_back(std::move(k0), std::move(k1));
+    with_bool(stats != nullptr, [&](auto pf) {
+        with_bool(merged != nullptr, [&](auto mg) {
+            hipExtLaunchKernelGGL((k_rootwalk<8, decltype(pf)::value, decltype(mg)::value>), dim3(grid), dim3(64), 0,
+                                  h->stream, k0, k1, 0, ray, n, perm, (const Node8 *)h->d_nodes.p,
+                                  (const ExactRec *)h->d_xrec.p, eps, max_ray_len, skey, scnt, stats, Q, SP,
+                                  ds ? ds->nd : nullptr, SA);
+        });
+    });
+    if (*sampled) h->prof.ev_kern.emplace_back(std::move(k0), std::move(k1));
     RETIF(run_spill_levels(h, in, rs, n, perm, eps, max_ray_len, skey, scnt, stats, SP, ds ? ds->nd : nullptr));
     if (h->host_prof >= 2) {                          // diagnostic: this launch's hand-over queue lengths
         uint32_t q[8] = {0};
@@ -1013,13 +994,6 @@ static int run_queue(lpc_handle *h, const RaysIn &in, const float *rs, int64_t n
     return 0;
 }
 
-// intersect for n rays of `in` into the slot arrays, and optionally into a
-// caller's [ray][mesh] buffers (st_user != NULL, the reference's scratch layout).
-// traced != NULL (trace iterations without per-ray exports): the launch works in
-// its coherence order and *traced receives the rays in that order.
-// ds != NULL (a speculative trace iteration, chained traced population): n is
-// the bound, the kernels read the population size on the device and the
-// launch shapes follow ds->pred.
 // the side stream of the sliver kernels and its fork / join events, created on
 // first use (a handle whose slivers run in the walk's grid holds one stream, so
 // several handles in flight each keep a hardware queue of their own); false:
@@ -1038,10 +1012,40 @@ static bool side_stream(lpc_handle *h)
     return h->stream2 && h->ev_side[0] && h->ev_side[1];
 }
 
-static int run_intersect(lpc_handle *h, const RaysIn &in, int64_t n, float max_ray_len,
-                         float *st_user, int32_t *si_user, int32_t *sc_user,
-                         double dmax2 = INFINITY, RaysIn *traced = nullptr, const DevSize *ds = nullptr)
+// One intersect launch's inputs and outputs (run_intersect).  The drop-in calls
+// leave trace / traced / ds at their defaults: no cull, no masks.
+struct IsectIn {
+    RaysIn rays;
+    int64_t n = 0;
+    float max_ray_len = 0.0f;
+    double dmax2 = INFINITY;                        // max |D|^2 of the rays (sliver pieces in reach)
+    float *st_user = nullptr;                       // optional: the caller's [ray][mesh] distances,
+    int32_t *si_user = nullptr, *sc_user = nullptr; //   triangle indices, counts
+    const DevSize *ds = nullptr;
+    bool trace = false;                             // an iteration of the trace, over its population ...
+    bool traced = false;                            // ... without per-ray exports
+};
+struct IsectOut {
+    RaysIn traced;                                  // IsectIn::traced: the rays in the launch's order
+    uint32_t *tmask = nullptr;                      // this launch's written-slot masks (k_shade_stage reads them)
+    bool sampled = false;                           // the walk launch carries profiling events
+};
+
+// intersect for a.n rays of a.rays into the slot arrays, and optionally into a
+// caller's [ray][mesh] buffers (st_user != NULL, the reference's scratch layout).
+// a.traced (trace iterations without per-ray exports): the launch works in
+// its coherence order and out->traced receives the rays in that order.
+// a.ds != NULL (a speculative trace iteration, chained traced population): n is
+// the bound, the kernels read the population size on the device and the
+// launch shapes follow ds->pred.
+static int run_intersect(lpc_handle *h, const IsectIn &a, IsectOut *out)
 {
+    const RaysIn &in = a.rays;
+    int64_t n = a.n;
+    const float max_ray_len = a.max_ray_len;
+    const DevSize *ds = a.ds;
+    const bool traced = a.traced;
+    *out = IsectOut();
     RETIF(ensure_ws(h, n));
     const int64_t nb = n;                          // capacity
     if (ds) n = std::max<int64_t>(1, std::min(ds->pred, nb));   // launch shapes
@@ -1050,7 +1054,7 @@ static int run_intersect(lpc_handle *h, const RaysIn &in, int64_t n, float max_r
     // the pieces of the root items: q_level's cut (the same sliver pieces at every
     // cut), coarser while k_roots_s cannot hold them (tiny populations)
     PieceTable *pt;
-    int32_t g = q_level(h, n, traced && h->pop_traced);
+    int32_t g = q_level(h, n, traced && h->pop.traced);
     RETIF(piece_table(h, &pt, g));
     // (a table of more than 1 024 run roots, g = 1, goes to k_roots_s in batches)
     while (pt->npieces > LPC_ROOTS_BATCH && g > 1) {
@@ -1071,7 +1075,7 @@ static int run_intersect(lpc_handle *h, const RaysIn &in, int64_t n, float max_r
     h->acc_pending = false;
     // traced mode: the children come out in their parents' traced order and need
     // no sort of their own
-    const bool chained_pop = traced && h->pop_traced;
+    const bool chained_pop = traced && h->pop.traced;
     // a chained population keeps its parents' order, except a large one
     // (LPC_RESORT_MIN): after many generations that order has lost its coherence
     const bool sorted = n >= kSortMin && (!chained_pop || (!ds && n >= h->resort_min));
@@ -1085,13 +1089,14 @@ static int run_intersect(lpc_handle *h, const RaysIn &in, int64_t n, float max_r
     // of a trace's chained populations; "emitted" = the trace's first population,
     // whatever the export mode; the drop-in kernels (lpc_intersect,
     // lpc_bounce_host: no trace population) are never culled.  0: off.
-    h->half_roots = h->in_trace && h->half == 3 && !h->pop_emitted;
-    const bool restore = traced != nullptr;
+    const bool half = a.trace && h->half == 3 && !h->pop.emitted;
+    const bool restore = traced;
     const bool clean = restore && h->slots_clean && h->slots_mrl == max_ray_len;
     // written-slot masks: kept by every flush of this launch, read by its
     // k_shade_stage (restore path only; a mask bit may be stale, never missing:
     // the masks are cleared with the slots, and only the restore path reads them)
-    h->tm_cur = (restore && h->K <= 32) ? (uint32_t *)h->w_tm.p : nullptr;
+    uint32_t *const tmask = (restore && h->K <= 32) ? (uint32_t *)h->w_tm.p : nullptr;
+    out->tmask = tmask;
     const bool misc_clean = restore && h->misc_clean;
     h->slots_clean = h->misc_clean = false;
     SlotInit SIk = SI;
@@ -1126,9 +1131,9 @@ static int run_intersect(lpc_handle *h, const RaysIn &in, int64_t n, float max_r
         int32_t *vin = (int32_t *)(kout + C), *vout = vin + C;
         // the emitted rays' varying key bits (set_rays)
         int b0 = 0, b1 = 32;
-        if (traced && h->pop_emitted) { b0 = h->init_key_lo; b1 = h->init_key_hi; }
+        if (traced && h->pop.emitted) { b0 = h->init_key_lo; b1 = h->init_key_hi; }
         const int nbits = b1 - b0;
-        if (traced && h->pop_emitted && h->init_bsort && nbits >= 1 && nbits <= 16 && n >= LPC_MISC_WORDS) {
+        if (traced && h->pop.emitted && h->init_bsort && nbits >= 1 && nbits <= 16 && n >= LPC_MISC_WORDS) {
             // counting sort (MSD, two 8-bit digits, stable), then the gather
             const int hb = std::min(nbits, LPC_BS_HB), lb = nbits - hb;
             const int64_t nblk = (n + LPC_BS_RPB - 1) / LPC_BS_RPB;
@@ -1148,7 +1153,7 @@ static int run_intersect(lpc_handle *h, const RaysIn &in, int64_t n, float max_r
         } else {
             // a re-sorted chained population: the key (5-D Morton) spans its own box
             // (k_stage_move of the iteration that made it), not the scene's
-            const uint32_t *pbox = (traced && chained_pop && h->pbox_ok) ? (const uint32_t *)h->d_pbox.p : nullptr;
+            const uint32_t *pbox = (traced && chained_pop && h->pop.pbox_ok) ? (const uint32_t *)h->d_pbox.p : nullptr;
             hipLaunchKernelGGL(k_raykey, dim3(grid1(n)), dim3(256), 0, h->stream, in, n, h->box_lo[0], h->box_lo[1],
                                h->box_lo[2], h->box_scale[0], h->box_scale[1], h->box_scale[2], kin, vin,
                                (float4 *)h->w_aos.p, SIk, pbox, pbox ? kKeyObits : 5, pbox ? 1 : 0);
@@ -1168,14 +1173,11 @@ static int run_intersect(lpc_handle *h, const RaysIn &in, int64_t n, float max_r
             QueueShape shf;
             RETIF(queue_args(h, n, pt, nullptr, &Qf, &shf));
             const dim3 gg((unsigned)((n + 1023) / 1024));
-            if (h->half_roots)
-                hipLaunchKernelGGL(k_gather_roots<true>, gg, dim3(1024), 0, h->stream, (const float4 *)h->w_aos.p,
-                                   n, perm, (float *)h->w_rs.p, traced ? 1 : 0, (const Piece *)pt->pieces.p,
-                                   (int)pt->npieces, Qf);
-            else
-                hipLaunchKernelGGL(k_gather_roots<false>, gg, dim3(1024), 0, h->stream, (const float4 *)h->w_aos.p,
-                                   n, perm, (float *)h->w_rs.p, traced ? 1 : 0, (const Piece *)pt->pieces.p,
-                                   (int)pt->npieces, Qf);
+            with_bool(half, [&](auto hf) {
+                hipLaunchKernelGGL(k_gather_roots<decltype(hf)::value>, gg, dim3(1024), 0, h->stream,
+                                   (const float4 *)h->w_aos.p, n, perm, (float *)h->w_rs.p, traced ? 1 : 0,
+                                   (const Piece *)pt->pieces.p, (int)pt->npieces, Qf);
+            });
             roots_done = true;
         } else {
             hipLaunchKernelGGL(k_gather_aos, dim3(grid1(n)), dim3(256), 0, h->stream, (const float4 *)h->w_aos.p, n,
@@ -1190,15 +1192,15 @@ static int run_intersect(lpc_handle *h, const RaysIn &in, int64_t n, float max_r
             RaysIn t;
             t.ox = f; t.oy = f + n; t.oz = f + 2 * n; t.dx = f + 3 * n; t.dy = f + 4 * n; t.dz = f + 5 * n;
             t.pw = f + 6 * n; t.pmid = (const int32_t *)(f + 7 * n);
-            *traced = t;
+            out->traced = t;
         } else {
-            *traced = in;
+            out->traced = in;
         }
         perm = nullptr;
     }
     unsigned long long *stats = h->prof.stats ? (unsigned long long *)h->prof.d_stats.p : nullptr;
     // sliver pieces the launch's rays can reach: dmin <= max |D| (sliver_dmin)
-    if (!(dmax2 >= 0.0)) dmax2 = INFINITY;          // NaN bound (a NaN direction): no culling
+    const double dmax2 = a.dmax2 >= 0.0 ? a.dmax2 : INFINITY;   // NaN bound (a NaN direction): no culling
     const float dmax = (float)std::min<double>(sqrt(dmax2 * (1.0 + 1e-5)), (double)INFINITY);
     int32_t nsp = 0;
     while (nsp < pt->nspieces && (ds || pt->sdmin[(size_t)nsp] <= dmax)) ++nsp;
@@ -1226,7 +1228,7 @@ static int run_intersect(lpc_handle *h, const RaysIn &in, int64_t n, float max_r
         A.R = in; A.rs = rs; A.n = n; A.perm = perm; A.pk = (const PacketRec *)h->w_pk.p;
         A.srec = (const SliverRec *)h->d_srec.p; A.pieces = (const Piece *)pt->spieces.p; A.nsp = nsp;
         A.ppw = (int)ppw; A.eps = eps; A.max_ray_len = max_ray_len; A.dmax = dmax;
-        A.skey = skey; A.scnt = scnt; A.stats = stats; A.nd = nd_dev; A.dm2d = dm2_dev; A.tmask = h->tm_cur;
+        A.skey = skey; A.scnt = scnt; A.stats = stats; A.nd = nd_dev; A.dm2d = dm2_dev; A.tmask = tmask;
         return A;
     };
     auto launch_slivers = [&]() -> int {
@@ -1247,28 +1249,27 @@ static int run_intersect(lpc_handle *h, const RaysIn &in, int64_t n, float max_r
     if (!side && !merge_try) RETIF(launch_slivers());       // no side stream: before the walk, this stream
     Event e0, e1;
     if (h->prof.on && !h->prof.light) { e0 = ev_get(h); e1 = ev_get(h); (void)hipEventRecord(e0, h->stream); }
-    h->prof.sampled = false;
     if (pt->npieces > 0) {
         const SliverArgs SAm = sliver_args(kSliverMergePpw);
         RETIF(run_queue(h, in, rs, n, perm, pt, eps, max_ray_len, skey, scnt, stats, ds, merge_try ? &SAm : nullptr,
-                        roots_done));
+                        roots_done, half, tmask, &out->sampled));
     }
     if (h->prof.on) {      // the intersect stage: the walk (+ k_packet, k_slivers)
         if (!h->prof.light) {
             (void)hipEventRecord(e1, h->stream);
             h->prof.ev_isect.emplace_back(std::move(e0), std::move(e1));
         }
-        if (!h->prof.light || h->prof.sampled) {
+        if (!h->prof.light || out->sampled) {
             h->prof.launches += 1;
             h->prof.pairs += n * (int64_t)h->M;
         }
     }
     if (side) RETIF(launch_slivers());
     if (side) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_side[1], 0));
-    if (st_user) {
+    if (a.st_user) {
         hipLaunchKernelGGL(k_slot_export, dim3(grid1(n)), dim3(256), 0, h->stream, n, h->K,
                            (const int32_t *)h->d_live.p, (const unsigned long long *)skey,
-                           (const int32_t *)scnt, st_user, si_user, sc_user, 1);
+                           (const int32_t *)scnt, a.st_user, a.si_user, a.sc_user, 1);
     }
     HIPCHK(h, hipGetLastError());
     return 0;
@@ -1291,15 +1292,10 @@ static ShadeArgs shade_args(lpc_handle *h, const RaysIn &in, const int32_t *meas
 static int run_shade(lpc_handle *h, const RaysIn &in, const int32_t *meas_in, int64_t n,
                      float max_ray_len, float ior_env, bool extra)
 {
-    ShadeArgs A;
-    A.in = in; A.meas_in = meas_in; A.n = n; A.K = h->K;
-    A.skey = (const unsigned long long *)h->w_key.p; A.sc = (const int32_t *)h->w_sc.p;
-    A.mat_type = (const int32_t *)h->d_mat.p; A.ior = (const float *)h->d_ior.p;
-    A.refl = (const float *)h->d_refl.p; A.diss = (const float *)h->d_diss.p;
-    A.verts = (const float *)h->d_verts.p;
-    A.max_ray_len = max_ray_len; A.ior_env = ior_env;
-    A.o = shade_ptrs(h, extra);
-    LPC_KU_LAUNCH(h, k_shade, dim3(grid1(n)), dim3(256), h->stream, A);
+    const ShadeArgs A = shade_args(h, in, meas_in, n, max_ray_len, ior_env, extra);
+    with_ku(h->K, [&](auto ku) {
+        hipLaunchKernelGGL(k_shade<decltype(ku)::value>, dim3(grid1(n)), dim3(256), 0, h->stream, A);
+    });
     HIPCHK(h, hipGetLastError());
     return 0;
 }
@@ -1691,14 +1687,6 @@ static int upload_rays(lpc_handle *h, Pop &P, int64_t n, const float *origin4, c
     return 0;
 }
 
-static int copy_pop(lpc_handle *h, Pop &dst, const Pop &src, int64_t n)
-{
-    for (int k = 0; k < 7; ++k)
-        HIPCHK(h, hipMemcpyAsync(dst.f(k), src.f(k), (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(dst.pmid(), src.pmid(), (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
-    return 0;
-}
-
 int lpc_bounce_host(lpc_handle *h, int64_t n, const float *origin4, const float *dir4,
                     float *pow, int32_t *meas, const int32_t *prev_mid, float max_ray_len,
                     float ior_env, float *dest4, int32_t *isect_mid, float *r_dir4, float *r_pow,
@@ -1727,7 +1715,8 @@ int lpc_bounce_host(lpc_handle *h, int64_t n, const float *origin4, const float 
         rc = upload_rays(h, P, nc, origin4 + 4 * base, dir4 + 4 * base, pow + base, prev_mid + base);
         if (rc) break;
         if (hipMemcpy(dmeas.p, meas + base, (size_t)nc * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = set_err(h, LPC_E_HIP, "meas upload"); break; }
-        rc = run_intersect(h, P.in(), nc, max_ray_len, nullptr, nullptr, nullptr, bdmax2);
+        IsectOut io;
+        rc = run_intersect(h, IsectIn{P.in(), nc, max_ray_len, bdmax2}, &io);
         if (!rc) rc = run_shade(h, P.in(), (const int32_t *)dmeas.p, nc, max_ray_len, ior_env, true);
         if (rc) break;
         ShadeOutPtrs o = shade_ptrs(h, true);
@@ -1788,8 +1777,9 @@ int lpc_intersect(lpc_handle *h, int64_t n, const float *dev_origin4, const floa
         RaysIn in;
         in.ox = s; in.oy = s + Cw; in.oz = s + 2 * Cw; in.dx = s + 3 * Cw; in.dy = s + 4 * Cw;
         in.dz = s + 5 * Cw; in.pw = nullptr; in.pmid = nullptr;
-        RETIF(run_intersect(h, in, nc, max_ray_len, dev_tmin + base * h->K, dev_itmp + base * h->K,
-                            dev_cnt + base * h->K));
+        IsectOut io;
+        RETIF(run_intersect(h, IsectIn{in, nc, max_ray_len, INFINITY, dev_tmin + base * h->K, dev_itmp + base * h->K,
+                                       dev_cnt + base * h->K}, &io));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     RETIF(check_qerr(h));
@@ -1881,15 +1871,6 @@ int lpc_set_chunk(lpc_handle *h, int64_t rays_per_chunk)
     return 0;
 }
 
-static int reset_measured(lpc_handle *h)
-{
-    h->m_total = 0;
-    DevAcc z;
-    memset(&z, 0, sizeof(z));
-    HIPCHK(h, hipMemcpy(h->d_acc.p, &z, sizeof(z), hipMemcpyHostToDevice));
-    return 0;
-}
-
 // May the emitted rays' coherence sort be the counting sort (k_bkey..k_bsort2)?
 // Its second level runs one block per hi bucket, so it pays only when no bucket
 // is large: the hi-digit counts of k_raykey's key that k_ray_scan counted for
@@ -1968,13 +1949,8 @@ int lpc_trace_reset(lpc_handle *h)
     HIPCHK(h, hipSetDevice(h->device));
     // the first iteration reads the emitted rays where set_rays put them (I is
     // never written by an iteration: no copy)
-    h->pop_init = true;
+    h->pop = PopState{h->n_init, h->init_dmax2, /*init*/ true, /*traced*/ false, /*emitted*/ true, /*pbox_ok*/ false};
     h->mp_valid = true;                             // until an iteration does not sum it
-    h->n_cur = h->n_init;
-    h->pop_traced = false;
-    h->pop_emitted = true;
-    h->pop_dmax2 = h->init_dmax2;
-    h->pbox_ok = false;
     h->m_total = 0;                             // measured record emptied (the first iteration resets the counters)
     h->m_inflight = 0;
     // the culled-power ledger goes with the measured record (stream-ordered:
@@ -2180,10 +2156,6 @@ static int xchg_stats(lpc_handle *h, const lpc_iter_stats &S, lpc_iter_stats *G)
     return 0;
 }
 
-static int trace_run(lpc_handle *h, int32_t max_iter, double power_threshold, lpc_iter_stats *per_iter,
-                     int32_t *n_iter, int64_t *measured_count, double *mesh_power, int32_t mesh_power_cap,
-                     bool wait);
-
 // A rank that fails locally still takes part in the exchange its peers wait in,
 // with the failure flag (slot 0) set: they see it in the sums and fail at once
 // (xchg_stats, the trace-end sums) instead of waiting for a rank that left, and
@@ -2323,7 +2295,7 @@ int lpc_sync(lpc_handle *h)
 int lpc_trace_population(lpc_handle *h, int64_t *n)
 {
     if (!h || !n) return set_err(h, LPC_E_ARG, "null argument");
-    *n = h->n_cur;
+    *n = h->pop.n;
     return 0;
 }
 
@@ -2378,15 +2350,14 @@ struct Pending {
     int64_t n_in = 0;           // its population (-1: device-sized, known once the iteration before is read)
     unsigned seq = 0;           // mapped ring slot / sequence number (early)
     bool early = false;         // counters through the mapped ring (else copy + sync)
-    bool traced = false;        // its children come out in traced order
-    bool fused = false;         // k_shade_stage + k_stage_move: it wrote the next IterCtl entry
+    bool fused = false;         // traced (its children come out in traced order), k_shade_stage +
+                                //   k_stage_move: it wrote the next IterCtl entry
     bool mp_fused = false;      // it summed the measured power per measure mesh
     bool ds = false;            // device-sized (speculative)
     bool empty = false;         // nothing to do (n_in 0, host-sized)
     int64_t n_bound = 0;        // device-sized: population bound
     double thr = -INFINITY;     // fused: the stop threshold its k_stage_move applied (ds_thr)
-    // host state before its enqueue (undo of a discarded speculative iteration)
-    bool was_init = false, was_traced = false, was_emitted = false, was_pbox = false;
+    PopState before;            // the population's role before its enqueue (undo of a discarded speculative iteration)
 };
 
 // A results export (lpc_trace_iterate_export): the caller's host block and
@@ -2466,50 +2437,224 @@ static int export_chunk(lpc_handle *h, const RaysIn &in, const ShadeOutPtrs &o, 
     return 0;
 }
 
-// Enqueue one iteration over the current population (host-sized: h->n_cur rays;
+// Where an iteration's per-ray results go (iter_enqueue).  Empty: nowhere, and the
+// iteration runs fused, in traced order.
+struct IterOut {
+    float *origin4 = nullptr, *dest4 = nullptr, *pow = nullptr;
+    int32_t *meas = nullptr;
+    float *next_pow = nullptr;              // the kept children's power (iter_collect copies it)
+    const ExportSpec *X = nullptr;          // results export (lpc_trace_iterate_export)
+    bool per_ray() const { return origin4 || dest4 || pow || meas; }
+};
+
+// What the chunks of one enqueued iteration share.
+struct IterPlan {
+    int64_t N = 0, C = 0;                   // the population (device-sized: its bound), rays per chunk
+    const DevSize *ds = nullptr;
+    DevAcc *host_acc = nullptr;             // early: the mapped ring slot the counters are published to
+    unsigned seq = 0;
+    bool want_box = false;                  // fused: the chunks write the children's origin box (d_pbox)
+    bool cut = false;                       // power cutoff: the compaction's CUT instantiations ...
+    CullSumArgs CS;                         // ... and the ledger's arguments (both cull_setup's)
+};
+
+// Power cutoff: this launch's per-tile culled sums and the iteration's ledger
+// slot (a device-sized iteration is enqueued while the iteration before it is
+// uncollected: the slot after its).  Off: I->CS stays zero.
+static int cull_setup(lpc_handle *h, IterPlan *I)
+{
+    CullSumArgs *CS = &I->CS;
+    memset(CS, 0, sizeof(*CS));
+    I->cut = h->min_power > 0.0f;
+    if (!I->cut) return 0;
+    const int64_t slot = h->it_done + (I->ds ? 1 : 0);
+    if (slot >= kCullSlots)
+        return set_err(h, LPC_E_STATE, "trace: the culled-power ledger holds " + std::to_string(kCullSlots) +
+                                           " iterations");
+    if (!h->d_cull.p) {
+        RETIF(dalloc(h, h->d_cull, (size_t)kCullSlots * sizeof(CullSlot)));
+        HIPCHK(h, hipMemsetAsync(h->d_cull.p, 0, h->d_cull.bytes, h->stream));
+    }
+    const size_t nt_ws = ((size_t)h->ws_rays + LPC_ST_TILE - 1) / LPC_ST_TILE;
+    RETIF(dalloc(h, h->w_cull, nt_ws * (8 + 4) + 64));
+    CS->cp = (const double *)h->w_cull.p;
+    CS->cc = (const uint32_t *)(CS->cp + nt_ws);
+    CS->slot = (CullSlot *)h->d_cull.p + slot;
+    h->cull_dirty = true;
+    return 0;
+}
+
+// Power cutoff: the chunk's culled sums into the ledger slot, off the counters' publication.
+static void cull_sum(lpc_handle *h, const IterPlan &I, int64_t base, int64_t ntiles, int tile, const long long *nd)
+{
+    CullSumArgs CS = I.CS;
+    CS.first = base == 0 ? 1 : 0;
+    CS.ntiles = ntiles; CS.tile = tile; CS.nd = nd;
+    hipLaunchKernelGGL(k_cull_sum, dim3(1), dim3(256), 0, h->stream, CS);
+}
+
+// One chunk of a traced iteration: shade + staged compaction, two kernels
+// (k_shade_stage, k_stage_move; several chunks: each places its rows after the
+// earlier chunks', refracted rows staged in T, k_append at the end).  tmask: the
+// written-slot masks of the chunk's run_intersect.
+static int enqueue_fused_chunk(lpc_handle *h, const IterPlan &I, const RaysIn &in, uint32_t *tmask, int64_t base,
+                               int64_t nc)
+{
+    const DevSize *ds = I.ds;
+    const size_t mc = (size_t)h->m_cap;
+    float *mf = (float *)h->m_buf.p;
+    const size_t Cs = (size_t)h->ws_rays;
+    const int64_t ntc = (int64_t)((Cs + LPC_ST_TILE - 1) / LPC_ST_TILE);   // staging tile arrays' stride
+    // device-sized: grid from the expected size (grid-stride over the actual tiles)
+    const int64_t ng_rays = ds ? std::max<int64_t>(1, std::min(ds->pred, nc)) : nc;
+    const int64_t nt = (ng_rays + LPC_ST_TILE - 1) / LPC_ST_TILE;
+    const int64_t nt_max = (nc + LPC_ST_TILE - 1) / LPC_ST_TILE;     // tiles the launch may touch
+    StageArgs G;
+    G.S = shade_args(h, in, nullptr, nc, h->max_ray_len, h->ior_env, false);
+    G.nd = ds ? ds->nd : nullptr;
+    G.stR = (float *)h->w_shf.p; G.stT = (float *)h->w_shi.p;   // the 20 shade-output arrays hold the staging rows
+    G.stM = (float *)h->w_soa.p; G.cst = (int64_t)Cs;
+    G.tpow = (double *)h->w_fc.p; G.tcnt = (uint32_t *)(G.tpow + ntc); G.tdm = G.tcnt + ntc;
+    G.skey = (unsigned long long *)h->w_key.p; G.scnt = (int32_t *)h->w_sc.p;
+    // measured power per measure mesh summed on the way (no k_mesh_sum at the trace end)
+    G.nmp = h->meas_meshes.size() <= (size_t)LPC_MP_MAX ? (int)h->meas_meshes.size() : 0;
+    for (int m = 0; m < LPC_MP_MAX; ++m) G.mpm[m] = m < G.nmp ? h->meas_meshes[(size_t)m] : -1;
+    G.tmp = (double *)(G.tdm + ntc);            // 16 ntc bytes in: 8-aligned
+    const int64_t ng = (nt_max + LPC_ST_GROUP - 1) / LPC_ST_GROUP;
+    unsigned long long *gs = (unsigned long long *)h->w_gsum.p;
+    G.gsum = gs + (size_t)h->gpar * (size_t)h->gcap;
+    G.tmask = tmask;
+    G.tbox = I.want_box ? (uint32_t *)h->w_tbox.p : nullptr;
+    G.cut = h->min_power; G.tcc = (uint32_t *)I.CS.cc; G.tcp = (double *)I.CS.cp;
+    with_bool(I.cut, [&](auto ct) {     // (this nesting keeps the instantiations in their order in the code object)
+        with_bool(ds != nullptr, [&](auto dsz) {
+            with_ku(h->K, [&](auto ku) {
+                hipLaunchKernelGGL((k_shade_stage<decltype(ku)::value, decltype(dsz)::value, decltype(ct)::value>),
+                                   dim3((unsigned)nt), dim3(LPC_ST_TILE), 0, h->stream, G);
+            });
+        });
+    });
+    MoveArgs M;
+    M.ntiles = nt_max; M.ngroups = ng;
+    M.stR = G.stR; M.stT = G.stT; M.stM = G.stM; M.cst = G.cst;
+    M.tcnt = G.tcnt; M.tpow = G.tpow; M.tdm = G.tdm; M.nmp = G.nmp; M.tmp = G.tmp; M.gsum = G.gsum;
+    M.popR = h->B.f(0); M.capR = h->B.cap;
+    M.mrec = mf; M.capM = (int64_t)mc; M.m_base = (unsigned long long)h->m_total;
+    M.acc = (DevAcc *)h->d_acc.p; M.host_acc = I.host_acc; M.seq = I.seq;
+    M.misc = (uint32_t *)h->d_misc.p;
+    M.mrun = (double *)h->d_mrun.p;
+    M.gsum_next = gs + (size_t)(1 - h->gpar) * (size_t)h->gcap;
+    M.gdirty_next = h->gdirty[1 - h->gpar];
+    M.ctl = (IterCtl *)h->d_ctl.p; M.par = h->ctl_par;
+    M.thr = h->ds_thr; M.nmax = ds_cap(h); M.dcap2 = h->dcap * h->dcap * (1.0 - 1e-6);
+    M.tbox = G.tbox; M.pbox = G.tbox ? (uint32_t *)h->d_pbox.p : nullptr;
+    M.popT = nullptr; M.capT = 0; M.cbase_in = nullptr; M.cbase_out = nullptr;
+    M.first = 1; M.last = 1;
+    if (I.C < I.N) {                    // chunk base / C of several
+        const int64_t k = base / I.C;
+        unsigned long long *cb = (unsigned long long *)h->d_cbase.p;
+        M.popT = h->T.f(0); M.capT = h->T.cap;
+        M.cbase_in = cb + (k & 1) * 3; M.cbase_out = cb + ((k & 1) ^ 1) * 3;
+        M.first = base == 0 ? 1 : 0;
+        M.last = base + nc >= I.N ? 1 : 0;
+        if (!M.last) { M.host_acc = nullptr; M.ctl = nullptr; }   // the last chunk publishes the totals
+    }
+    h->gdirty[1 - h->gpar] = 0;
+    h->gdirty[h->gpar] = ng;            // this launch's k_shade_stage adds into its first ng groups
+    h->gpar = 1 - h->gpar;
+    with_bool(ds != nullptr, [&](auto dsz) {
+        hipLaunchKernelGGL(k_stage_move<decltype(dsz)::value>, dim3((unsigned)nt), dim3(LPC_ST_TILE), 0, h->stream, M);
+    });
+    if (I.cut) cull_sum(h, I, base, nt_max, LPC_ST_TILE, ds ? ds->nd : nullptr);
+    h->slots_clean = true;              // k_shade_stage restored what it read
+    h->slots_mrl = h->max_ray_len;
+    h->misc_clean = true;               // k_stage_move reset the next launch's words
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// A chunk's per-ray results into the caller's arrays, synchronously (lpc_trace_iterate).
+static int copy_per_ray(lpc_handle *h, const IterOut &O, const RaysIn &in, const ShadeOutPtrs &o, int64_t base,
+                        int64_t nc)
+{
+    // the copies below run on the null stream: the shading on h->stream first
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    auto pack = [&](float *dst4, const float *x, const float *y, const float *z) -> int {
+        hipLaunchKernelGGL(k_pack4, dim3(grid1(nc)), dim3(256), 0, h->stream, nc, x, y, z,
+                           (float4 *)h->w_stage.p);
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipMemcpy(dst4 + 4 * base, h->w_stage.p, (size_t)nc * 16, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    if (O.origin4) RETIF(pack(O.origin4, in.ox, in.oy, in.oz));
+    if (O.dest4) RETIF(pack(O.dest4, o.destx, o.desty, o.destz));
+    if (O.pow) HIPCHK(h, hipMemcpy(O.pow + base, o.pw, (size_t)nc * 4, hipMemcpyDeviceToHost));
+    if (O.meas) HIPCHK(h, hipMemcpy(O.meas + base, o.meas, (size_t)nc * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// One chunk of an iteration with per-ray results: k_shade, then the compaction
+// in three kernels (k_count, k_scan, k_scatter), the results taken in between.
+static int enqueue_plain_chunk(lpc_handle *h, const IterPlan &I, const IterOut &O, const RaysIn &in, int64_t base,
+                               int64_t nc)
+{
+    const size_t mc = (size_t)h->m_cap;
+    float *mf = (float *)h->m_buf.p;
+    const ShadeOutPtrs o = shade_ptrs(h, false);
+    CompactArgs A;
+    A.n = nc; A.nb = (nc + 1023) / 1024; A.o = o;
+    A.blk_cnt = (int32_t *)h->w_blk_cnt.p; A.blk_off = (long long *)h->w_blk_off.p;
+    A.blk_pow = (double *)h->w_blk_pow.p; A.acc = (DevAcc *)h->d_acc.p;
+    A.nR = h->B.out(); A.nT = h->T.out();
+    A.direct_t = (I.C >= I.N) ? 1 : 0;                  // one chunk: no refracted staging
+    if (A.direct_t) A.nT = A.nR;
+    A.mx = mf; A.my = mf + mc; A.mz = mf + 2 * mc; A.mp = mf + 3 * mc;
+    A.mm = (int32_t *)(mf + 4 * mc);
+    A.host_acc = I.host_acc;
+    A.seq = I.seq;
+    A.cut = h->min_power; A.blk_cc = (uint32_t *)I.CS.cc; A.blk_cp = (double *)I.CS.cp;
+    RETIF(run_shade(h, in, nullptr, nc, h->max_ray_len, h->ior_env, false));
+    with_bool(I.cut, [&](auto ct) {
+        hipLaunchKernelGGL(k_count<decltype(ct)::value>, dim3((unsigned)A.nb), dim3(256), 0, h->stream, A);
+    });
+    if (I.cut) cull_sum(h, I, base, A.nb, 1024, nullptr);
+    if (O.X) {
+        const double hx = h->host_prof ? host_us() : 0.0;
+        RETIF(export_chunk(h, in, o, nc, base, I.N, *O.X));
+        if (h->host_prof) fprintf(stderr, "[lpc host]   export chunk %.1f us\n", host_us() - hx);
+    }
+    if (O.per_ray()) RETIF(copy_per_ray(h, O, in, o, base, nc));
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, h->stream, A);
+    with_bool(I.cut, [&](auto ct) {
+        hipLaunchKernelGGL(k_scatter<decltype(ct)::value>, dim3((unsigned)A.nb), dim3(256), 0, h->stream, A);
+    });
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// Enqueue one iteration over the current population (host-sized: h->pop.n rays;
 // ds != NULL: device-sized, traced single-chunk only).  Host bookkeeping that
-// needs no counters (population roles) happens here; iter_collect the rest.
-static int iter_enqueue(lpc_handle *h, float *out_origin4, float *out_dest4, float *out_pow, int32_t *out_meas,
-                        float *out_next_pow, const DevSize *ds, Pending *P, const ExportSpec *X = nullptr)
+// needs no counters (the population's role) happens here; iter_collect the rest.
+static int iter_enqueue(lpc_handle *h, const IterOut &O, const DevSize *ds, Pending *P)
 {
     *P = Pending();
-    P->was_init = h->pop_init; P->was_traced = h->pop_traced; P->was_emitted = h->pop_emitted;
-    P->was_pbox = h->pbox_ok;
-    const int64_t N = ds ? ds->bound : h->n_cur;
+    P->before = h->pop;
+    IterPlan I;
+    const int64_t N = I.N = ds ? ds->bound : h->pop.n;
     P->n_in = ds ? -1 : N;
     P->ds = ds != nullptr;
     P->n_bound = N;
     if (N == 0) { P->empty = true; return 0; }
-    const int64_t C = std::min(N, chunk_rays(h));
+    const int64_t C = I.C = std::min(N, chunk_rays(h));
     if (ds && C < N) return set_err(h, LPC_E_STATE, "internal: device-sized iteration over one chunk only");
+    I.ds = ds;
     const double hp0 = h->host_prof ? host_us() : 0.0;
     RETIF(ensure_ws(h, C));
     RETIF(pop_reserve(h, h->B, 2 * N));
     if (!ds) RETIF(pop_reserve(h, h->T, N));
     // measured rows: the iterations still in flight may append up to their populations
     RETIF(ensure_measured(h, h->m_total + h->m_inflight + N));
-    // power cutoff: the compaction's CUT instantiations, this launch's per-tile
-    // culled sums and the iteration's ledger slot (a device-sized iteration is
-    // enqueued while the iteration before it is uncollected: the slot after its)
-    const bool cut = h->min_power > 0.0f;
-    CullSumArgs CS;
-    memset(&CS, 0, sizeof(CS));
-    if (cut) {
-        const int64_t slot = h->it_done + (ds ? 1 : 0);
-        if (slot >= kCullSlots)
-            return set_err(h, LPC_E_STATE, "trace: the culled-power ledger holds " + std::to_string(kCullSlots) +
-                                               " iterations");
-        if (!h->d_cull.p) {
-            RETIF(dalloc(h, h->d_cull, (size_t)kCullSlots * sizeof(CullSlot)));
-            HIPCHK(h, hipMemsetAsync(h->d_cull.p, 0, h->d_cull.bytes, h->stream));
-        }
-        const size_t nt_ws = ((size_t)h->ws_rays + LPC_ST_TILE - 1) / LPC_ST_TILE;
-        RETIF(dalloc(h, h->w_cull, nt_ws * (8 + 4) + 64));
-        CS.cp = (const double *)h->w_cull.p;
-        CS.cc = (const uint32_t *)(CS.cp + nt_ws);
-        CS.slot = (CullSlot *)h->d_cull.p + slot;
-        h->cull_dirty = true;
-    }
+    RETIF(cull_setup(h, &I));
     if (h->host_prof)
         fprintf(stderr, "[lpc host]   buffers %.1f us (m_total %lld inflight %lld m_cap %lld)\n", host_us() - hp0,
                 (long long)h->m_total, (long long)h->m_inflight, (long long)h->m_cap);
@@ -2523,183 +2668,40 @@ static int iter_enqueue(lpc_handle *h, float *out_origin4, float *out_dest4, flo
         hipLaunchKernelGGL(k_acc_init, dim3(1), dim3(64), 0, h->stream, (DevAcc *)h->d_acc.p,
                            (unsigned long long)h->m_total);
     }
-    const size_t mc = (size_t)h->m_cap;
-    float *mf = (float *)h->m_buf.p;
-    // traced mode: one chunk, no per-ray export (the population then comes out in
-    // its parents' coherence order; measured rays per iteration likewise)
-    const bool exports = out_origin4 || out_dest4 || out_pow || out_meas || out_next_pow || X;
-    const bool traced = !exports;
+    // traced mode: no per-ray export (the population then comes out in its
+    // parents' coherence order; measured rays per iteration likewise), shaded and
+    // compacted fused (enqueue_fused_chunk)
+    const bool traced = !(O.per_ray() || O.next_pow || O.X);
     // the counters come back through the mapped host ring k_scan / k_stage_move
     // write, so the host decides and launches the next iteration while the rows
     // still move (profiling: only the light level, whose events end before)
-    const bool early = h->acc_map_dev && (C >= N || traced) && !out_next_pow && (!h->prof.on || h->prof.light);
+    const bool early = h->acc_map_dev && (C >= N || traced) && !O.next_pow && (!h->prof.on || h->prof.light);
     ++h->acc_seq;
-    P->seq = h->acc_seq;
+    P->seq = I.seq = h->acc_seq;
     P->early = early;
-    P->traced = traced;
-    // traced: k_shade_stage + k_stage_move (several chunks: each places its rows
-    // after the earlier chunks', refracted rows staged in T, k_append at the end)
-    const bool fused = traced;
-    if (fused && C < N) RETIF(dalloc(h, h->d_cbase, 8 * sizeof(unsigned long long)));
-    if (ds && !(fused && early)) return set_err(h, LPC_E_STATE, "internal: device-sized iteration off the fused path");
-    P->fused = fused;
+    if (traced && C < N) RETIF(dalloc(h, h->d_cbase, 8 * sizeof(unsigned long long)));
+    if (ds && !(traced && early)) return set_err(h, LPC_E_STATE, "internal: device-sized iteration off the fused path");
+    P->fused = traced;
     P->thr = h->ds_thr;
-    const size_t Cs = (size_t)h->ws_rays;
-    const int64_t ntc = (int64_t)((Cs + LPC_ST_TILE - 1) / LPC_ST_TILE);   // staging tile arrays' stride
-    IterCtl *ctl = (IterCtl *)h->d_ctl.p;
-    const int par = h->ctl_par;
-    bool box_made = false;                  // the fused chunks wrote the children's box (d_pbox)
+    // fused: it sums the measured power per measure mesh when they fit (StageArgs::nmp)
+    P->mp_fused = traced && h->meas_meshes.size() <= (size_t)LPC_MP_MAX;
+    I.host_acc = early ? h->acc_map_dev + P->seq % kAccRing : nullptr;
+    // fused: the children's origin box when they may be re-sorted (population >= LPC_RESORT_MIN)
+    I.want_box = traced && !ds && 2 * N >= h->resort_min;
+    IsectIn ii;
+    ii.max_ray_len = h->max_ray_len; ii.dmax2 = h->pop.dmax2; ii.ds = ds;
+    ii.trace = true; ii.traced = traced;
+    const bool timed = h->prof.on && !h->prof.light;
     for (int64_t base = 0; base < N; base += C) {
-        const int64_t nc = std::min(C, N - base);
-        RaysIn in = (h->pop_init ? h->I : h->A).in(base);
-        RaysIn tin;
-        h->in_trace = true;
-        const int rc_i = run_intersect(h, in, nc, h->max_ray_len, nullptr, nullptr, nullptr, h->pop_dmax2,
-                                       traced ? &tin : nullptr, ds);
-        h->in_trace = false;
-        RETIF(rc_i);
-        if (traced) in = tin;
-        Event e0, e1;
-        if (h->prof.on && !h->prof.light) { e0 = ev_get(h); e1 = ev_get(h); (void)hipEventRecord(e0, h->stream); }
-        ShadeOutPtrs o = shade_ptrs(h, false);
-        CompactArgs A;
-        A.n = nc; A.nb = (nc + 1023) / 1024; A.o = o;
-        A.blk_cnt = (int32_t *)h->w_blk_cnt.p; A.blk_off = (long long *)h->w_blk_off.p;
-        A.blk_pow = (double *)h->w_blk_pow.p; A.acc = (DevAcc *)h->d_acc.p;
-        A.nR = h->B.out(); A.nT = h->T.out();
-        A.direct_t = (C >= N) ? 1 : 0;                      // one chunk: no refracted staging
-        if (A.direct_t) A.nT = A.nR;
-        A.mx = mf; A.my = mf + mc; A.mz = mf + 2 * mc; A.mp = mf + 3 * mc;
-        A.mm = (int32_t *)(mf + 4 * mc);
-        A.host_acc = early ? h->acc_map_dev + P->seq % kAccRing : nullptr;
-        A.seq = P->seq;
-        A.cut = h->min_power; A.blk_cc = (uint32_t *)CS.cc; A.blk_cp = (double *)CS.cp;
-        CS.first = base == 0 ? 1 : 0;
-        if (fused) {                  // shade + staged compaction, two kernels (k_shade_stage, k_stage_move)
-            // device-sized: grid from the expected size (grid-stride over the actual tiles)
-            const int64_t ng_rays = ds ? std::max<int64_t>(1, std::min(ds->pred, nc)) : nc;
-            const int64_t nt = (ng_rays + LPC_ST_TILE - 1) / LPC_ST_TILE;
-            const int64_t nt_max = (nc + LPC_ST_TILE - 1) / LPC_ST_TILE;     // tiles the launch may touch
-            StageArgs G;
-            G.S = shade_args(h, in, nullptr, nc, h->max_ray_len, h->ior_env, false);
-            G.nd = ds ? ds->nd : nullptr;
-            G.stR = (float *)h->w_shf.p;                // the 20 shade-output arrays hold the staging rows
-            G.stT = (float *)h->w_shi.p;
-            G.stM = (float *)h->w_soa.p;
-            G.cst = (int64_t)Cs;
-            G.tpow = (double *)h->w_fc.p;
-            G.tcnt = (uint32_t *)(G.tpow + ntc);
-            G.tdm = G.tcnt + ntc;
-            G.skey = (unsigned long long *)h->w_key.p;
-            G.scnt = (int32_t *)h->w_sc.p;
-            // measured power per measure mesh summed on the way (no k_mesh_sum at the trace end)
-            G.nmp = h->meas_meshes.size() <= (size_t)LPC_MP_MAX ? (int)h->meas_meshes.size() : 0;
-            for (int m = 0; m < LPC_MP_MAX; ++m) G.mpm[m] = m < G.nmp ? h->meas_meshes[(size_t)m] : -1;
-            G.tmp = (double *)(G.tdm + ntc);            // 16 ntc bytes in: 8-aligned
-            const int64_t ng = (nt_max + LPC_ST_GROUP - 1) / LPC_ST_GROUP;
-            unsigned long long *gs = (unsigned long long *)h->w_gsum.p;
-            G.gsum = gs + (size_t)h->gpar * (size_t)h->gcap;
-            G.tmask = h->tm_cur;            // set by this chunk's run_intersect
-            // the children's origin box when they may be re-sorted (population >= LPC_RESORT_MIN)
-            const bool want_box = !ds && 2 * N >= h->resort_min;
-            G.tbox = want_box ? (uint32_t *)h->w_tbox.p : nullptr;
-            G.cut = h->min_power; G.tcc = A.blk_cc; G.tcp = A.blk_cp;
-
-            if (cut) {
-                if (ds) LPC_KU_LAUNCH3(h, k_shade_stage, true, true, dim3((unsigned)nt), dim3(LPC_ST_TILE), h->stream, G);
-                else LPC_KU_LAUNCH3(h, k_shade_stage, false, true, dim3((unsigned)nt), dim3(LPC_ST_TILE), h->stream, G);
-            } else if (ds) LPC_KU_LAUNCH2(h, k_shade_stage, true, dim3((unsigned)nt), dim3(LPC_ST_TILE), h->stream, G);
-            else LPC_KU_LAUNCH2(h, k_shade_stage, false, dim3((unsigned)nt), dim3(LPC_ST_TILE), h->stream, G);
-            MoveArgs M;
-            M.ntiles = nt_max;
-            M.stR = G.stR; M.stT = G.stT; M.stM = G.stM; M.cst = G.cst;
-            M.tcnt = G.tcnt; M.tpow = G.tpow; M.tdm = G.tdm;
-            M.popR = h->B.f(0); M.capR = h->B.cap;
-            M.mrec = mf; M.capM = (int64_t)mc;
-            M.m_base = (unsigned long long)h->m_total;
-            M.acc = (DevAcc *)h->d_acc.p;
-            M.host_acc = A.host_acc;
-            M.seq = A.seq;
-            M.misc = (uint32_t *)h->d_misc.p;
-            M.nmp = G.nmp;
-            M.tmp = G.tmp;
-            M.mrun = (double *)h->d_mrun.p;
-            M.gsum = G.gsum;
-            M.ngroups = ng;
-            M.gsum_next = gs + (size_t)(1 - h->gpar) * (size_t)h->gcap;
-            M.gdirty_next = h->gdirty[1 - h->gpar];
-            M.ctl = ctl;
-            M.par = par;
-            M.thr = h->ds_thr;
-            M.nmax = ds_cap(h);
-            M.dcap2 = h->dcap * h->dcap * (1.0 - 1e-6);
-            M.tbox = G.tbox;
-            M.pbox = G.tbox ? (uint32_t *)h->d_pbox.p : nullptr;
-            box_made = G.tbox != nullptr;
-            M.popT = nullptr; M.capT = 0; M.cbase_in = nullptr; M.cbase_out = nullptr;
-            M.first = 1; M.last = 1;
-            if (C < N) {                        // chunk base / C of several
-                const int64_t k = base / C;
-                unsigned long long *cb = (unsigned long long *)h->d_cbase.p;
-                M.popT = h->T.f(0); M.capT = h->T.cap;
-                M.cbase_in = cb + (k & 1) * 3; M.cbase_out = cb + ((k & 1) ^ 1) * 3;
-                M.first = base == 0 ? 1 : 0;
-                M.last = base + nc >= N ? 1 : 0;
-                if (!M.last) { M.host_acc = nullptr; M.ctl = nullptr; }   // the last chunk publishes the totals
-            }
-            h->gdirty[1 - h->gpar] = 0;
-            h->gdirty[h->gpar] = ng;            // this launch's k_shade_stage adds into its first ng groups
-            h->gpar = 1 - h->gpar;
-            P->mp_fused = G.nmp > 0 || h->meas_meshes.empty();
-            if (ds) hipLaunchKernelGGL(k_stage_move<true>, dim3((unsigned)nt), dim3(LPC_ST_TILE), 0, h->stream, M);
-            else hipLaunchKernelGGL(k_stage_move<false>, dim3((unsigned)nt), dim3(LPC_ST_TILE), 0, h->stream, M);
-            if (cut) {                          // the ledger, off the counters' publication
-                CS.ntiles = nt_max; CS.tile = LPC_ST_TILE; CS.nd = ds ? ds->nd : nullptr;
-                hipLaunchKernelGGL(k_cull_sum, dim3(1), dim3(256), 0, h->stream, CS);
-            }
-            h->slots_clean = true;              // k_shade_stage restored what it read
-            h->slots_mrl = h->max_ray_len;
-            h->misc_clean = true;               // k_stage_move reset the next launch's words
-            HIPCHK(h, hipGetLastError());
-            if (h->prof.on && !h->prof.light) {
-                (void)hipEventRecord(e1, h->stream);
-                h->prof.ev_rest.emplace_back(std::move(e0), std::move(e1));
-            }
-            continue;
-        }
-        RETIF(run_shade(h, in, nullptr, nc, h->max_ray_len, h->ior_env, false));
-        if (cut) {
-            hipLaunchKernelGGL(k_count<true>, dim3((unsigned)A.nb), dim3(256), 0, h->stream, A);
-            CS.ntiles = A.nb; CS.tile = 1024; CS.nd = nullptr;
-            hipLaunchKernelGGL(k_cull_sum, dim3(1), dim3(256), 0, h->stream, CS);
-        } else {
-            hipLaunchKernelGGL(k_count<false>, dim3((unsigned)A.nb), dim3(256), 0, h->stream, A);
-        }
-        if (X) {
-            const double hx = h->host_prof ? host_us() : 0.0;
-            RETIF(export_chunk(h, in, o, nc, base, N, *X));
-            if (h->host_prof) fprintf(stderr, "[lpc host]   export chunk %.1f us\n", host_us() - hx);
-        }
-        if (out_origin4 || out_dest4 || out_pow || out_meas) {
-            // the copies below run on the null stream: the shading on h->stream first
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            auto pack = [&](float *dst4, const float *x, const float *y, const float *z) -> int {
-                hipLaunchKernelGGL(k_pack4, dim3(grid1(nc)), dim3(256), 0, h->stream, nc, x, y, z,
-                                   (float4 *)h->w_stage.p);
-                HIPCHK(h, hipStreamSynchronize(h->stream));
-                HIPCHK(h, hipMemcpy(dst4 + 4 * base, h->w_stage.p, (size_t)nc * 16, hipMemcpyDeviceToHost));
-                return 0;
-            };
-            if (out_origin4) RETIF(pack(out_origin4, in.ox, in.oy, in.oz));
-            if (out_dest4) RETIF(pack(out_dest4, o.destx, o.desty, o.destz));
-            if (out_pow) HIPCHK(h, hipMemcpy(out_pow + base, o.pw, (size_t)nc * 4, hipMemcpyDeviceToHost));
-            if (out_meas) HIPCHK(h, hipMemcpy(out_meas + base, o.meas, (size_t)nc * 4, hipMemcpyDeviceToHost));
-        }
-        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, h->stream, A);
-        if (cut) hipLaunchKernelGGL(k_scatter<true>, dim3((unsigned)A.nb), dim3(256), 0, h->stream, A);
-        else hipLaunchKernelGGL(k_scatter<false>, dim3((unsigned)A.nb), dim3(256), 0, h->stream, A);
-        HIPCHK(h, hipGetLastError());
-        if (h->prof.on && !h->prof.light) {
+        const int64_t nc = ii.n = std::min(C, N - base);
+        ii.rays = (h->pop.init ? h->I : h->A).in(base);
+        IsectOut io;
+        RETIF(run_intersect(h, ii, &io));
+        Event e0, e1;                   // profiling: the chunk's remaining kernels
+        if (timed) { e0 = ev_get(h); e1 = ev_get(h); (void)hipEventRecord(e0, h->stream); }
+        if (traced) RETIF(enqueue_fused_chunk(h, I, io.traced, io.tmask, base, nc));
+        else RETIF(enqueue_plain_chunk(h, I, O, ii.rays, base, nc));
+        if (timed) {
             (void)hipEventRecord(e1, h->stream);
             h->prof.ev_rest.emplace_back(std::move(e0), std::move(e1));
         }
@@ -2712,12 +2714,9 @@ static int iter_enqueue(lpc_handle *h, float *out_origin4, float *out_dest4, flo
         HIPCHK(h, hipGetLastError());
     }
     h->ctl_par ^= 1;                    // the next iteration reads the entry this one's k_stage_move writes
-    // the children are the next population (their counts come with iter_collect)
-    h->pbox_ok = box_made;
+    // the children are the next population (their count and max |D|^2 come with iter_collect)
     std::swap(h->A, h->B);
-    h->pop_init = false;
-    h->pop_traced = traced;
-    h->pop_emitted = false;
+    h->pop = PopState{h->pop.n, h->pop.dmax2, /*init*/ false, traced, /*emitted*/ false, /*pbox_ok*/ I.want_box};
     h->inflight = true;                 // k_stage_move / k_scatter may still run
     return 0;
 }
@@ -2755,7 +2754,7 @@ static int iter_collect(lpc_handle *h, const Pending &P, float *out_next_pow, lp
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     if (h->prof.on) prof_resolve(h);
-    h->n_cur = nR + nT;
+    h->pop.n = nR + nT;
     h->m_total = (int64_t)acc.m_total;
     // the running per-mesh measured power stays valid while every iteration sums it
     h->mp_valid = h->mp_valid && P.mp_fused;
@@ -2766,7 +2765,7 @@ static int iter_collect(lpc_handle *h, const Pending &P, float *out_next_pow, lp
     float dm2;
     memcpy(&dm2, &acc.dmax2_bits, 4);
     RETIF(check_dcap(h, (double)dm2));
-    h->pop_dmax2 = (double)dm2;                 // the next population's max |D|^2 (float, see run_intersect)
+    h->pop.dmax2 = (double)dm2;                 // the next population's max |D|^2 (float, see run_intersect)
     if (st) *st = S;
     return 0;
 }
@@ -2793,10 +2792,10 @@ static void iter_discard(lpc_handle *h, const Pending &P)
     h->m_inflight -= P.n_bound;
     if (P.empty) return;
     std::swap(h->A, h->B);
-    h->pop_init = P.was_init;
-    h->pop_traced = P.was_traced;
-    h->pop_emitted = P.was_emitted;
-    h->pbox_ok = P.was_pbox;
+    // the size and max |D|^2 are iter_collect's, not the enqueue's: they stay
+    const PopState now = h->pop;
+    h->pop = P.before;
+    h->pop.n = now.n; h->pop.dmax2 = now.dmax2;
 }
 
 int lpc_trace_iterate(lpc_handle *h, float *out_origin4, float *out_dest4, float *out_pow,
@@ -2807,7 +2806,7 @@ int lpc_trace_iterate(lpc_handle *h, float *out_origin4, float *out_dest4, float
     if (!h->traced_ready) return set_err(h, LPC_E_STATE, "trace_iterate before trace_set_rays");
     HIPCHK(h, hipSetDevice(h->device));
     Pending P;
-    RETIF(iter_enqueue(h, out_origin4, out_dest4, out_pow, out_meas, out_next_pow, nullptr, &P));
+    RETIF(iter_enqueue(h, IterOut{out_origin4, out_dest4, out_pow, out_meas, out_next_pow}, nullptr, &P));
     if (h->host_prof && !P.empty)
         fprintf(stderr, "[lpc host] n %lld  launch %.1f us\n", (long long)P.n_in, host_us() - t_enter);
     return iter_collect(h, P, out_next_pow, st);
@@ -2820,11 +2819,11 @@ int lpc_trace_iterate_export(lpc_handle *h, void *host, int32_t flags, lpc_iter_
     if (!h->traced_ready) return set_err(h, LPC_E_STATE, "trace_iterate_export before trace_set_rays");
     HIPCHK(h, hipSetDevice(h->device));
     const double t_enter = h->host_prof ? host_us() : 0.0;
-    ExportSpec X;
-    X.host = (char *)host;
-    X.org = (flags & 1) ? 1 : 0;
+    const ExportSpec X{(char *)host, (flags & 1) ? 1 : 0};
+    IterOut O;
+    O.X = &X;
     Pending P;
-    RETIF(iter_enqueue(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &P, &X));
+    RETIF(iter_enqueue(h, O, nullptr, &P));
     if (h->host_prof && !P.empty)
         fprintf(stderr, "[lpc host] n %lld  export launch %.1f us\n", (long long)P.n_in, host_us() - t_enter);
     return iter_collect(h, P, nullptr, st);
@@ -2834,9 +2833,9 @@ int lpc_trace_population_power(lpc_handle *h, float *out)
 {
     if (!h || !out) return set_err(h, LPC_E_ARG, "null argument");
     RETIF(settle(h));
-    if (h->n_cur > 0) {
-        const Pop &P = h->pop_init ? h->I : h->A;
-        HIPCHK(h, hipMemcpy(out, P.f(6), (size_t)h->n_cur * 4, hipMemcpyDeviceToHost));
+    if (h->pop.n > 0) {
+        const Pop &P = h->pop.init ? h->I : h->A;
+        HIPCHK(h, hipMemcpy(out, P.f(6), (size_t)h->pop.n * 4, hipMemcpyDeviceToHost));
     }
     return 0;
 }
@@ -2904,7 +2903,7 @@ static int trace_run(lpc_handle *h, int32_t max_iter, double power_threshold, lp
     h->gstats.clear();
     // the prediction: the last trace from emitted rays with this iteration limit
     // (which iterations it reached, populations relative to the first)
-    const int64_t n0 = h->pop_emitted ? h->n_cur : -1;
+    const int64_t n0 = h->pop.emitted ? h->pop.n : -1;
     const bool hist_ok = n0 > 0 && h->hist_iter == max_iter && !h->hist_r.empty();
     h->dcap_rebuilt = false;
     std::vector<int64_t> seen;
@@ -2935,7 +2934,7 @@ static int trace_run(lpc_handle *h, int32_t max_iter, double power_threshold, lp
     for (int32_t i = 0; i < max_iter; ++i) {
         if (!have_cur) {
             h->ds_thr = local_thr(i);
-            if ((rc = iter_enqueue(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &cur))) break;
+            if ((rc = iter_enqueue(h, IterOut(), nullptr, &cur))) break;
             have_cur = true;
         }
         // iteration i + 1, device-sized, while iteration i runs (its population is
@@ -2954,7 +2953,7 @@ static int trace_run(lpc_handle *h, int32_t max_iter, double power_threshold, lp
                 D.pred = std::max<int64_t>(1, std::min(pred_n, bound));
                 D.bound = bound;
                 h->ds_thr = local_thr(i + 1);
-                if ((rc = iter_enqueue(h, nullptr, nullptr, nullptr, nullptr, nullptr, &D, &nxt))) break;
+                if ((rc = iter_enqueue(h, IterOut(), &D, &nxt))) break;
                 have_nxt = true;
             }
         }
@@ -3271,10 +3270,9 @@ int lpc_elev_hist(lpc_handle *h, int64_t n, const float *pos4, const float *pwr,
     A.H = (double *)(d + o_H);
     A.elev_out = elev_out ? (double *)(d + o_e) : nullptr;
     if (n > 0) {
-        if (nbins <= LPC_ELEV_LDS_BINS)
-            hipLaunchKernelGGL(k_elev_hist<true>, dim3(elev_grid(h, n, 8)), dim3(256), 0, h->stream, A);
-        else
-            hipLaunchKernelGGL(k_elev_hist<false>, dim3(elev_grid(h, n, 8)), dim3(256), 0, h->stream, A);
+        with_bool(nbins <= LPC_ELEV_LDS_BINS, [&](auto lds) {
+            hipLaunchKernelGGL(k_elev_hist<decltype(lds)::value>, dim3(elev_grid(h, n, 8)), dim3(256), 0, h->stream, A);
+        });
         HIPCHK(h, hipGetLastError());
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));

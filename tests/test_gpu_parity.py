@@ -398,6 +398,67 @@ def test_clean_slots_across_paths(oracle_mod):
         np.testing.assert_array_equal(got[2], want[2])
 
 
+def test_dropin_calls_between_iterations_leave_trace_alone():
+    """A bounce and an lpc_intersect drop-in call on the handle between every two
+    trace iterations (few meshes: the written-slot masks are on) change nothing
+    of the trace, bit for bit, and the bounce gives a fresh handle's outputs."""
+    torch = pytest.importorskip("torch")
+    from lightpycl_amd.engine import Engine
+    sc = scenes.lens(n=3000, seed=31)
+    o4, d4, pw = rays_of(sc)
+    thr = (1.0 - sc.tau) * float(np.sum(pw, dtype=np.float64))
+    m = 1000
+    bo, bd, bp = o4[:m], d4[:m], pw[:m]
+    z, pm = np.zeros(m, np.int32), np.full(m, -2, np.int32)
+    dev = torch.device("cuda", 0)
+
+    def dropins(e):
+        g = e.bounce(bo, bd, bp, z, pm, sc.max_ray_len, sc.ior_env)
+        K = e.mesh_count
+        to, td = torch.from_numpy(bo).to(dev), torch.from_numpy(bd).to(dev)
+        tmin = torch.full((m, K), float(sc.max_ray_len), dtype=torch.float32, device=dev)
+        cnt = torch.zeros((m, K), dtype=torch.int32, device=dev)
+        itmp = torch.zeros((m, K), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        e._c(e.L.lpc_intersect(e.h, m, to.data_ptr(), td.data_ptr(), np.float32(sc.max_ray_len), tmin.data_ptr(),
+                               cnt.data_ptr(), itmp.data_ptr()))
+        return g
+
+    def trace(between):
+        e = Engine(0)
+        try:
+            e.upload_meshes(sc.meshes)
+            e.set_rays(o4, d4, pw, sc.max_ray_len, sc.ior_env)
+            stats, bounces = [], []
+            for i in range(sc.iterations):
+                if between and i > 0:
+                    bounces.append(dropins(e))
+                s, _ = e.iterate()
+                stats.append((s.n_in, s.n_reflect, s.n_refract, s.n_measured, s.power_next))
+                if s.power_next < thr or s.n_reflect + s.n_refract == 0:    # the trace loop's stop rule
+                    break
+            return stats, e.measured(), bounces
+        finally:
+            e.close()
+
+    plain, plain_meas, _ = trace(False)
+    mixed, mixed_meas, bounces = trace(True)
+    assert len(plain) >= 2 and len(bounces) == len(plain) - 1
+    assert mixed == plain
+    assert mixed_meas[0] == plain_meas[0]
+    np.testing.assert_array_equal(mixed_meas[1], plain_meas[1])
+    e = Engine(0)
+    try:
+        e.upload_meshes(sc.meshes)
+        want = e.bounce(bo, bd, bp, z, pm, sc.max_ray_len, sc.ior_env)
+    finally:
+        e.close()
+    for g in bounces:
+        assert g.keys() == want.keys()
+        for k in want:
+            np.testing.assert_array_equal(g[k], want[k], err_msg=k)
+
+
 @pytest.mark.parametrize("name,n", [("synthetic", 100000), ("lens", 30000)])
 def test_async_trace_run_equals_sync(name, n):
     """lpc_trace_run_async returns once the trace's outputs are final and lets
