@@ -137,6 +137,64 @@ const double kThin = 1.0;               // thin-triangle rule factor (thin_axis;
 // join events keep it (a device-scope release measured equal).
 static const unsigned kEvTimingFlags = hipEventDisableSystemFence;
 
+// The uploaded scene: what lpc_scene_upload and build_records produce.  Usable
+// only while `ready`: an upload validates its arguments on locals, then
+// scene_invalidate(), the members filled in place (the grow-only buffers are
+// kept), scene_publish() last.  An early return in between leaves "no scene".
+struct Scene {
+    bool ready = false;
+    int32_t M = 0, K = 0, Mpad = 0;
+    std::vector<float> hv[3];                       // host copies, made on demand from d_raw (rebuilds, profiling)
+    DBuf d_raw;                                     // the scene's v0 | v1 | v2 rows on the device ((M,4) each)
+    DBuf d_verts, d_mat, d_ior, d_refl, d_diss, d_nodes, d_srec, d_xrec;
+    DBuf d_live;                                    // [K] slot written by some run
+    std::vector<int32_t> run_lo, run_hi;
+    std::vector<std::vector<int32_t>> run_levels;    // per run: (first node, count) per level, root first
+    std::vector<FiltRec> node_self;                  // each node's own test (piece roots)
+    std::vector<int32_t> run_slo, run_shi;           // sliver records per run
+    std::vector<float> sliver_dmin_host;             // SliverRec::dmin, host copy
+    int64_t n_slivers = 0, n_thin = 0;               // ... of them thin triangles (thin_axis, k = 1)
+    std::vector<int32_t> slot_run, meas_meshes;
+    bool mat_passive = false;                       // no material can raise a ray's power (lpc_scene_upload)
+    float box_lo[3] = {0, 0, 0}, box_scale[3] = {1, 1, 1};
+    double scene_scale = 1.0, dcap = 16.0;           // half diagonal of the scene box (filter h), the filter's Dcap
+    std::map<std::vector<int32_t>, PieceTable> ptabs;   // by the hierarchy level each live run is cut at
+    DBuf d_fan;                                     // profiling: fan-triangle flags (SpillArgs::fan)
+};
+
+// What set_rays (host rows, device-born sources, a staged batch turning
+// current) records about the emitted rays in I; assigned whole (emitted_rays).
+struct Emitted {
+    bool ready = false;
+    int64_t n_init = 0;
+    double init_dmax2 = INFINITY;                   // max |D|^2 of the emitted rays
+    bool pow_nonneg = false;                        // every emitted power >= 0
+    int init_key_lo = 0, init_key_hi = 32;          // key bits that vary over the emitted rays
+    bool init_bsort = false;                        // their sort may be the counting sort (bsort_fits)
+    float max_ray_len = 1e3f, ior_env = 1.0f;
+};
+
+// Size switches and test hooks, read once from the environment in lpc_open;
+// only lpc_set_walk_grid and lpc_set_chunk write theirs afterwards.
+struct Knobs {
+    int half = 3;                                   // LPC_HALF: 3 = half-line cull at the piece roots of chained
+                                                    //   populations (run_intersect), 0 = off
+    int64_t chunk = 0;                              // LPC_CHUNK: rays per chunk (0 -> default)
+    int64_t resort_min = 2000000;                   // LPC_RESORT_MIN: chained traced populations from here re-sort
+    int64_t sliver_merge = 0;                       // LPC_SLIVER_MERGE: sliver units in k_rootwalk's grid from a size
+                                                    //   (0: always; -1: never, k_slivers on the side stream)
+    int64_t walk_grid = kWalkWaves;                 // LPC_WALK_GRID: k_rootwalk blocks
+    bool spec = true;                               // LPC_SPEC: speculative iterations (trace_run)
+    double dcap_init = 16.0;                        // LPC_DCAP_MILLI / 1000 (tests: a rebuild inside a trace)
+    int spill_budget = 20;                          // LPC_BUDGET: node visits before a wave hands its work over (0 off)
+    int64_t spill_large_per_tri = 16;               // LPC_LARGE_PER_TRI
+    int64_t spill_cap = (int64_t)1 << 22;           // LPC_SPILL_CAP: k_spill queue capacity (items)
+    int host_prof = 0;                              // LPC_HOSTPROF: host-side timing of each iteration (stderr);
+                                                    //   2: also each launch's hand-over queue lengths (synchronising)
+    int stage_mode = 0;                             // LPC_STAGE_MODE: 0 pageable DMA (round 6 A/B: 1.23-1.28 G fresh
+                                                    //   rays), 1 pinned rows (0.83-0.93), 2 pinned SoA chunks (0.77-1)
+};
+
 // Every GPU resource of the handle is held by an owner of lpc_resource.hpp and
 // goes with it; lpc_close names no member.  The one rule: members are destroyed
 // in reverse declaration order, so a stream is declared before everything that
@@ -148,30 +206,11 @@ struct lpc_handle {
     std::string err;
     char name[256] = {0};
     int cus = 0;
-    // scene
-    int32_t M = 0, K = 0, Mpad = 0;
-    std::vector<float> hv0, hv1, hv2;               // host copies, made on demand from d_raw (record rebuilds, profiling)
-    const float *src_v[3] = {nullptr, nullptr, nullptr};   // the scene's (n,4) rows: the caller's during
-                                                    //   lpc_scene_upload, hv0..2 after host_vertices()
-    DBuf d_raw;                                     // the scene's v0 | v1 | v2 rows on the device ((M,4) each)
-    std::vector<int32_t> run_lo, run_hi;
-    std::vector<std::vector<int32_t>> run_levels;    // per run: (first node, count) per level, root first
-    std::vector<FiltRec> node_self;                  // each node's own test (piece roots)
-    std::vector<float> sliver_dmin_host;             // SliverRec::dmin, host copy
-    double init_dmax2 = INFINITY;                    // max |D|^2 of the emitted rays
-    std::vector<int32_t> run_slo, run_shi;           // sliver records per run
-    int64_t n_slivers = 0;
-    int64_t n_thin = 0;                              // of them thin triangles (thin_axis, k = 1)
-    float box_lo[3] = {0, 0, 0}, box_scale[3] = {1, 1, 1};
-    double scene_scale = 1.0;                        // half diagonal of the scene box (filter h)
-    std::vector<int32_t> slot_run;
-    std::vector<int32_t> meas_meshes;
-    DBuf d_nodes, d_srec, d_xrec, d_verts, d_mat, d_ior, d_refl, d_diss;
-    double dcap = 16.0;
-    double dcap_init = 16.0;                        // LPC_DCAP_MILLI / 1000 (tests: a rebuild inside a trace)
-    std::map<std::vector<int32_t>, PieceTable> ptabs;   // by the hierarchy level each live run is cut at
+    Knobs knobs;
+    Scene scene;
+    int64_t scene_gen = 0;                          // scenes invalidated (a staged scan's key box)
+    Emitted emitted;                                // the rays in I
     // workspace
-    int64_t chunk = 0;                              // rays per chunk (0 -> default)
     int64_t ws_rays = 0;
     DBuf w_key, w_sc, w_rs, w_shf, w_shi, w_blk_cnt, w_blk_off, w_blk_pow;
     DBuf w_soa, w_stage, w_sort, w_sort_tmp;
@@ -181,10 +220,6 @@ struct lpc_handle {
     bool acc_pending = false;                       // next slot reset also resets the iteration counters
     int64_t acc_pending_total = 0;
     int64_t m_inflight = 0;                         // populations of the iterations enqueued, not yet read
-    int64_t walk_grid = kWalkWaves;                 // k_rootwalk blocks (lpc_set_walk_grid, LPC_WALK_GRID)
-    int64_t sliver_merge = 0;                       // LPC_SLIVER_MERGE: sliver units in k_rootwalk's grid from
-                                                    // this population size (0: always; -1: never,
-                                                    // k_slivers on the side stream)
     DBuf w_fc;                                      // k_shade_stage tile counts / power / max |dir|^2
     DBuf w_gsum;                                    // per 256-tile group counts, two buffers (zero when unused)
     int64_t gcap = 0;
@@ -193,39 +228,23 @@ struct lpc_handle {
     bool slots_clean = false;                       // every slot (max_ray_len slots_mrl, idx -1, count 0)
     float slots_mrl = 0.0f;
     bool misc_clean = false;                        // the launch words were reset for the next launch
-    int half = 3;                                   // LPC_HALF: 3 = half-line cull at the piece roots of chained
-                                                    //   populations (run_intersect), 0 = off
-    DBuf d_live;                                    // [K] slot written by some run
     DBuf w_pk;                                      // PacketRec per 128-ray wave (k_slivers)
     DBuf d_misc;                                    // LPC_MISC_WORDS per-launch words
     size_t sort_tmp_bytes = 0;
-    int64_t resort_min = 2000000;                   // chained traced populations from this size are sorted again
-    // work hand-over (LPC_BUDGET, LPC_SPILL_CAP, LPC_LARGE_PER_TRI: tests drive the
-    // queue-overflow and budget paths at small sizes)
-    int spill_budget = 20;                          // node visits before a wave hands over (0 off)
-    int64_t spill_large_per_tri = 16;
-    int64_t spill_cap = (int64_t)1 << 22;           // k_spill queue capacity (items)
     DBuf w_spill;                                   // k_spill queue
-    int init_key_lo = 0, init_key_hi = 32;          // key bits that vary over the emitted rays (set_rays)
-    bool init_bsort = false;                        // their sort may be the counting sort (bsort_fits)
     DBuf w_qroots;                                  // root items
     Pinned<DevAcc> acc_host;                        // pinned copy of d_acc (one read per iteration)
     Pinned<DevAcc> acc_map;                         // mapped pinned ring k_scan / k_stage_move publish into
     DevAcc *acc_map_dev = nullptr;                  // (slot seq % kAccRing; + device address)
     // speculative iterations (trace_run, LPC_SPEC): iteration i + 1 is enqueued
     // device-sized (IterCtl) before iteration i's counters are read
-    bool spec = true;
     DBuf d_ctl;                                     // IterCtl
     int ctl_par = 0;                                // the parity the next enqueued iteration reads
     double ds_thr = -INFINITY;                      // trace_run's power threshold (k_stage_move's stop rule)
-    bool mat_passive = false;                       // no material can raise a ray's power (lpc_scene_upload)
-    bool pow_nonneg = false;                        // every emitted power >= 0 (set_rays)
     std::vector<double> hist_r;                     // the last trace_run's populations / its first (the
     int32_t hist_iter = -1;                         //   speculation's prediction) and its iteration limit
     bool dcap_rebuilt = false;                      // check_dcap rebuilt the records (a speculative iteration is void)
     unsigned int acc_seq = 0;
-    int host_prof = 0;                              // LPC_HOSTPROF: host-side timing of each iteration (stderr);
-                                                    //   2: also each launch's hand-over queue lengths (synchronising)
     bool side_tried = false;                        // stream2 / ev_side created on first use (side_stream)
     // results export (lpc_trace_iterate_export): k_export packs a chunk's part of
     // the results tuple into xst[par] on the main stream, the export stream copies
@@ -254,9 +273,6 @@ struct lpc_handle {
     // trace
     Pop A, B, T, I;
     PopState pop;                                   // which of them is current, and as what
-    int64_t n_init = 0;
-    float max_ray_len = 1e3f, ior_env = 1.0f;
-    bool traced_ready = false;
     bool inflight = false;                          // the stream may still run a trace's last kernels (settle)
     DBuf m_buf;                                     // measured: x y z pw | mesh
     int64_t m_cap = 0, m_total = 0;
@@ -275,7 +291,6 @@ struct lpc_handle {
         int every = 1;                              // light mode: events on every every-th walk launch
         int64_t seq = 0;                            // ... walk launches seen
         DBuf d_stats;                               // walk counters
-        DBuf d_fan;                                 // fan-triangle flags of the scene (SpillArgs::fan)
     } prof;
     // ray-sharded trace (lpc_set_allreduce): the termination decisions and the
     // trace-end aggregates over all ranks
@@ -306,8 +321,6 @@ struct lpc_handle {
         Event ev_stage;                             // main-stream work before a stage call (cstream waits)
         RaySlot rslot[2];
         int rs_head = 0, rs_count = 0;
-        int stage_mode = 0;                         // LPC_STAGE_MODE: 0 pageable DMA (round 6 A/B: 1.23-1.28 G
-                                                    //   fresh rays), 1 pinned rows (0.83-0.93), 2 pinned SoA chunks (0.77-1.0)
         void join()                                 // the helpers use the handle: they end before anything goes
         {
             for (auto &s : rslot)
@@ -315,7 +328,6 @@ struct lpc_handle {
         }
         ~Staged() { join(); }
     } stage;
-    int64_t scene_gen = 0;                          // lpc_scene_upload count (the scan's key box)
 };
 
 static std::string g_open_err;
@@ -417,37 +429,49 @@ static int host_threads();
 static void host_parts(int64_t n, int T, const std::function<void(int64_t, int64_t, int)> &fn);
 static void host_pool_run(int n, const std::function<void(int)> &fn);
 
+// Host copies of the scene's rows, from the device (a filter-record rebuild or
+// the profiling fan flags after lpc_scene_upload returned).
+static int host_vertices(lpc_handle *h)
+{
+    Scene &sc = h->scene;
+    for (int k = 0; k < 3; ++k) {
+        if (sc.hv[k].size() == 4 * (size_t)sc.M) continue;
+        std::vector<float> v(4 * (size_t)sc.M);
+        HIPCHK(h, hipMemcpy(v.data(), (const float *)sc.d_raw.p + (size_t)k * 4 * sc.M, (size_t)sc.M * 16,
+                            hipMemcpyDeviceToHost));
+        sc.hv[k].swap(v);
+    }
+    return 0;
+}
+
 // Per mesh run: an 8-wide sphere hierarchy over its triangles in a top-down
 // median-split order, every node's test node_record() of ALL triangles below it
 // (so the slack does not compound from level to level); triangles whose sphere
 // test is degenerate (slivers) or far wider than the triangle (thin) go to the
 // run's line-filter list; triangles that can never be hit are dropped.  Results
 // do not depend on the order (ties are resolved by triangle index).
-static int host_vertices(lpc_handle *h);
-
-static int build_records(lpc_handle *h)
+// The scene is not ready from here until the caller publishes it; allocations
+// and copies come first, the host tables last.
+static int build_records(lpc_handle *h, const float *const *rows = nullptr)
 {
-    h->ptabs.clear();       // pieces index the records built here
-    if (!h->src_v[0]) RETIF(host_vertices(h));       // a rebuild after the upload: the rows from the device
+    Scene &sc = h->scene;
+    sc.ready = false;
+    sc.ptabs.clear();       // pieces index the records built here
+    if (!rows) RETIF(host_vertices(h));              // a rebuild after the upload: the rows from the device
     SceneBuildIn in;
-    in.v0 = h->src_v[0]; in.v1 = h->src_v[1]; in.v2 = h->src_v[2];
-    in.run_lo = h->run_lo.data(); in.run_hi = h->run_hi.data(); in.nr = h->run_lo.size();
-    in.dcap = h->dcap; in.scene_scale = h->scene_scale; in.thin_k = kThin; in.stack_max = LPC_STACK;
+    in.v0 = rows ? rows[0] : sc.hv[0].data(); in.v1 = rows ? rows[1] : sc.hv[1].data();
+    in.v2 = rows ? rows[2] : sc.hv[2].data();
+    in.run_lo = sc.run_lo.data(); in.run_hi = sc.run_hi.data(); in.nr = sc.run_lo.size();
+    in.dcap = sc.dcap; in.scene_scale = sc.scene_scale; in.thin_k = kThin; in.stack_max = LPC_STACK;
     SceneBuildOut out;
-    const double t0 = h->host_prof ? host_us() : 0.0;
+    const double t0 = h->knobs.host_prof ? host_us() : 0.0;
     const std::string err = build_scene_records(in, out, [](int n, const std::function<void(int)> &fn) {
         host_pool_run(n, fn);
     });
     if (!err.empty()) return set_err(h, LPC_E_ARG, err);
-    if (h->host_prof)
+    if (h->knobs.host_prof)
         fprintf(stderr, "[lpc host] scene records %.1f us (%zu nodes, %zu slivers, %d threads)\n", host_us() - t0,
                 out.nodes.size(), out.slivers.size(), host_threads());
-    h->run_levels.swap(out.run_levels);
-    h->node_self.swap(out.node_self);
-    h->run_slo.swap(out.run_slo);
-    h->run_shi.swap(out.run_shi);
-    h->n_slivers = out.n_slivers;
-    h->n_thin = out.n_thin;
     // spare records so no buffer is empty
     if (out.nodes.empty()) { Node8 z; memset(&z, 0, sizeof(z)); out.nodes.push_back(z); }
     if (out.slivers.empty()) {
@@ -456,52 +480,39 @@ static int build_records(lpc_handle *h)
         ss.a = NAN; ss.idx = -1; ss.dmin = INFINITY;
         out.slivers.push_back(ss);
     }
-    h->sliver_dmin_host.clear();
-    for (const SliverRec &q : out.slivers) h->sliver_dmin_host.push_back(q.dmin);
-    h->Mpad = (int32_t)out.nodes.size();
     // exact records in leaf order (a leaf's 8 records are 384 contiguous bytes:
     // the walk stages them into LDS with one LDS-DMA load), each with its
     // triangle index; 8 spare records at the end, so the last leaf's load stays
     // inside the buffer (round 6; by triangle index before, A/B neutral)
     // (k_exact_records from the rows on the device and the leaf order)
-    const double tb0 = h->host_prof ? host_us() : 0.0;
+    const double tb0 = h->knobs.host_prof ? host_us() : 0.0;
     const size_t nx = out.xorder.size();
-    RETIF(dalloc(h, h->d_xrec, (nx + 8) * sizeof(ExactRec)));
+    RETIF(dalloc(h, sc.d_xrec, (nx + 8) * sizeof(ExactRec)));
     RETIF(dalloc(h, h->d_tmp, std::max<size_t>(nx, 1) * 4));
     if (nx) HIPCHK(h, hipMemcpy(h->d_tmp.p, out.xorder.data(), nx * 4, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemsetAsync((ExactRec *)h->d_xrec.p + nx, 0, 8 * sizeof(ExactRec), h->stream));
+    HIPCHK(h, hipMemsetAsync((ExactRec *)sc.d_xrec.p + nx, 0, 8 * sizeof(ExactRec), h->stream));
     if (nx) {
-        const float4 *raw = (const float4 *)h->d_raw.p;
+        const float4 *raw = (const float4 *)sc.d_raw.p;
         hipLaunchKernelGGL(k_exact_records, dim3(grid1((int64_t)nx)), dim3(256), 0, h->stream, (int64_t)nx,
-                           (const int32_t *)h->d_tmp.p, raw, raw + h->M, raw + 2 * (size_t)h->M,
-                           (ExactRec *)h->d_xrec.p);
+                           (const int32_t *)h->d_tmp.p, raw, raw + sc.M, raw + 2 * (size_t)sc.M,
+                           (ExactRec *)sc.d_xrec.p);
         HIPCHK(h, hipGetLastError());
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));      // d_tmp is reused
-    const double tb1 = h->host_prof ? host_us() : 0.0;
-    RETIF(dalloc(h, h->d_nodes, out.nodes.size() * sizeof(Node8)));
-    RETIF(dalloc(h, h->d_srec, out.slivers.size() * sizeof(SliverRec)));
-    HIPCHK(h, hipMemcpy(h->d_nodes.p, out.nodes.data(), out.nodes.size() * sizeof(Node8), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(h->d_srec.p, out.slivers.data(), out.slivers.size() * sizeof(SliverRec),
+    const double tb1 = h->knobs.host_prof ? host_us() : 0.0;
+    RETIF(dalloc(h, sc.d_nodes, out.nodes.size() * sizeof(Node8)));
+    RETIF(dalloc(h, sc.d_srec, out.slivers.size() * sizeof(SliverRec)));
+    HIPCHK(h, hipMemcpy(sc.d_nodes.p, out.nodes.data(), out.nodes.size() * sizeof(Node8), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(sc.d_srec.p, out.slivers.data(), out.slivers.size() * sizeof(SliverRec),
                         hipMemcpyHostToDevice));
-    if (h->host_prof)
+    if (h->knobs.host_prof)
         fprintf(stderr, "[lpc host] records upload: exact records %.1f us, nodes %.1f us\n", tb1 - tb0, host_us() - tb1);
-    return 0;
-}
-
-// Host copies of the scene's rows, from the device (a filter-record rebuild or
-// the profiling fan flags after lpc_scene_upload returned).
-static int host_vertices(lpc_handle *h)
-{
-    if (h->hv0.size() != 4 * (size_t)h->M) {
-        std::vector<float> *hv[3] = {&h->hv0, &h->hv1, &h->hv2};
-        for (int k = 0; k < 3; ++k) {
-            hv[k]->resize(4 * (size_t)h->M);
-            HIPCHK(h, hipMemcpy(hv[k]->data(), (const float *)h->d_raw.p + (size_t)k * 4 * h->M, (size_t)h->M * 16,
-                                hipMemcpyDeviceToHost));
-        }
-    }
-    for (int k = 0; k < 3; ++k) h->src_v[k] = (k == 0 ? h->hv0 : k == 1 ? h->hv1 : h->hv2).data();
+    sc.run_levels.swap(out.run_levels); sc.node_self.swap(out.node_self);
+    sc.run_slo.swap(out.run_slo); sc.run_shi.swap(out.run_shi);
+    sc.n_slivers = out.n_slivers; sc.n_thin = out.n_thin;
+    sc.sliver_dmin_host.clear();
+    for (const SliverRec &q : out.slivers) sc.sliver_dmin_host.push_back(q.dmin);
+    sc.Mpad = (int32_t)out.nodes.size();
     return 0;
 }
 
@@ -512,61 +523,56 @@ static int host_vertices(lpc_handle *h)
 // lane each).
 static int piece_table(lpc_handle *h, PieceTable **out, int32_t g)
 {
-    const size_t nr = h->run_levels.size();
+    const size_t nr = h->scene.run_levels.size();
     std::vector<int32_t> run_slot(nr, -1);
-    for (int32_t j = 0; j < h->K; ++j)
-        if (h->slot_run[(size_t)j] >= 0) run_slot[(size_t)h->slot_run[(size_t)j]] = j;
+    for (int32_t j = 0; j < h->scene.K; ++j)
+        if (h->scene.slot_run[(size_t)j] >= 0) run_slot[(size_t)h->scene.slot_run[(size_t)j]] = j;
     // the level each live run is cut at: the shallowest with >= g nodes (many g
     // give the same cut, so a scene builds only a few tables)
     std::vector<int32_t> cut(nr, -1);
     for (size_t r = 0; r < nr; ++r) {
         if (run_slot[r] < 0) continue;
-        const std::vector<int32_t> &L = h->run_levels[r];
+        const std::vector<int32_t> &L = h->scene.run_levels[r];
         size_t lv = 0;
         while (lv + 1 < L.size() / 2 && L[2 * lv + 1] < g) ++lv;
         cut[r] = L.empty() ? -2 : (int32_t)lv;
     }
-    auto it = h->ptabs.find(cut);
-    if (it != h->ptabs.end()) { *out = &it->second; return 0; }
+    auto it = h->scene.ptabs.find(cut);
+    if (it != h->scene.ptabs.end()) { *out = &it->second; return 0; }
     std::vector<Piece> pcs, spc, grp;
     std::vector<float> sdm;
+    auto piece_at = [&](int32_t root, int32_t slot) {   // a node's own test as a piece
+        Piece p;
+        memset(&p, 0, sizeof(p));
+        const FiltRec &t = h->scene.node_self[(size_t)root];
+        p.root = root; p.cx = t.cx; p.cy = t.cy; p.cz = t.cz; p.negB = t.negB; p.negA = t.negA;
+        p.slot = slot;
+        return p;
+    };
     for (size_t r = 0; r < nr; ++r) {
         if (run_slot[r] < 0) continue;
-        const std::vector<int32_t> &L = h->run_levels[r];
+        const std::vector<int32_t> &L = h->scene.run_levels[r];
         if (!L.empty()) {
             const size_t lv = (size_t)cut[r];
-            Piece gp;                   // the run root's own test over the run's pieces
-            memset(&gp, 0, sizeof(gp));
-            gp.root = L[0];
-            const FiltRec &gt = h->node_self[(size_t)gp.root];
-            gp.cx = gt.cx; gp.cy = gt.cy; gp.cz = gt.cz; gp.negB = gt.negB; gp.negA = gt.negA;
-            gp.slot = run_slot[r];
+            Piece gp = piece_at(L[0], run_slot[r]);     // the run root's own test over the run's pieces
             gp.s_lo = (int32_t)pcs.size();
             gp.s_hi = gp.s_lo + L[2 * lv + 1];
             grp.push_back(gp);
-            for (int32_t i = 0; i < L[2 * lv + 1]; ++i) {
-                Piece p;
-                memset(&p, 0, sizeof(p));
-                p.root = L[2 * lv] + i;
-                const FiltRec &t = h->node_self[(size_t)p.root];
-                p.cx = t.cx; p.cy = t.cy; p.cz = t.cz; p.negB = t.negB; p.negA = t.negA;
-                p.slot = run_slot[r];
-                pcs.push_back(p);
-            }
+            for (int32_t i = 0; i < L[2 * lv + 1]; ++i) pcs.push_back(piece_at(L[2 * lv] + i, run_slot[r]));
         }
-        for (int32_t a = h->run_slo[r]; a < h->run_shi[r]; a += 64) {
+        for (int32_t a = h->scene.run_slo[r]; a < h->scene.run_shi[r]; a += 64) {
             Piece p;
             memset(&p, 0, sizeof(p));
             p.root = -1;
             p.s_lo = a;
-            p.s_hi = std::min(a + 64, h->run_shi[r]);
+            p.s_hi = std::min(a + 64, h->scene.run_shi[r]);
             p.slot = run_slot[r];
             spc.push_back(p);
-            sdm.push_back(h->sliver_dmin_host[(size_t)a]);     // the run's slivers ascend in dmin
+            sdm.push_back(h->scene.sliver_dmin_host[(size_t)a]);     // the run's slivers ascend in dmin
         }
     }
     if (pcs.size() > 65535 || spc.size() > 65535) return set_err(h, LPC_E_ARG, "too many triangle pieces");
-    PieceTable &t = h->ptabs[cut];
+    PieceTable t;                       // cached only once complete
     t.npieces = (int32_t)pcs.size();
     t.nspieces = (int32_t)spc.size();
     {   // sliver pieces in ascending dmin: a launch takes the prefix its rays can reach
@@ -574,26 +580,22 @@ static int piece_table(lpc_handle *h, PieceTable **out, int32_t g)
         for (size_t i = 0; i < o.size(); ++i) o[i] = i;
         std::stable_sort(o.begin(), o.end(), [&](size_t x, size_t y) { return sdm[x] < sdm[y]; });
         std::vector<Piece> s2;
-        t.sdmin.clear();
         for (size_t i : o) { s2.push_back(spc[i]); t.sdmin.push_back(sdm[i]); }
         spc.swap(s2);
     }
-    if (!pcs.empty()) {
-        RETIF(dalloc(h, t.pieces, pcs.size() * sizeof(Piece)));
-        HIPCHK(h, hipMemcpy(t.pieces.p, pcs.data(), pcs.size() * sizeof(Piece), hipMemcpyHostToDevice));
-    }
-    if (!spc.empty()) {
-        RETIF(dalloc(h, t.spieces, spc.size() * sizeof(Piece)));
-        HIPCHK(h, hipMemcpy(t.spieces.p, spc.data(), spc.size() * sizeof(Piece), hipMemcpyHostToDevice));
-    }
+    auto put = [&](DBuf &b, const std::vector<Piece> &v) {
+        RETIF(dalloc(h, b, v.size() * sizeof(Piece)));
+        HIPCHK(h, hipMemcpy(b.p, v.data(), v.size() * sizeof(Piece), hipMemcpyHostToDevice));
+        return 0;
+    };
+    if (!pcs.empty()) RETIF(put(t.pieces, pcs));
+    if (!spc.empty()) RETIF(put(t.spieces, spc));
     // the gate pays when the runs are cut below their roots (<= 64 runs: one mask)
-    t.ngroups = 0;
     if (grp.size() <= 64 && grp.size() < pcs.size()) {
-        RETIF(dalloc(h, t.groups, grp.size() * sizeof(Piece)));
-        HIPCHK(h, hipMemcpy(t.groups.p, grp.data(), grp.size() * sizeof(Piece), hipMemcpyHostToDevice));
+        RETIF(put(t.groups, grp));
         t.ngroups = (int32_t)grp.size();
     }
-    *out = &t;
+    *out = &h->scene.ptabs.emplace(cut, std::move(t)).first->second;
     return 0;
 }
 
@@ -605,7 +607,6 @@ using RaySortCfg = rocprim::default_config;
 using RaySortOnesweep = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
                                                    rocprim::default_config, 0>;
 
-
 // Rays per chunk.  Default: as many as ~32 GB of per-chunk workspace holds (slots
 // 12 B per mesh + ~200 B of coherence copies, shade outputs and sort buffers per
 // ray), at most 128 Mi: a chunk is also the unit of the coherence sort, and large
@@ -613,8 +614,8 @@ using RaySortOnesweep = rocprim::radix_sort_config<rocprim::default_config, rocp
 // chunks than in 8 Mi ones.
 static int64_t chunk_rays(const lpc_handle *h)
 {
-    if (h->chunk > 0) return h->chunk;
-    const int64_t per_ray = (int64_t)12 * std::max(h->K, 1) + 200;
+    if (h->knobs.chunk > 0) return h->knobs.chunk;
+    const int64_t per_ray = (int64_t)12 * std::max(h->scene.K, 1) + 200;
     const int64_t c = ((int64_t)32 << 30) / per_ray;
     return std::max<int64_t>((int64_t)1 << 20, std::min<int64_t>((int64_t)128 << 20, c));
 }
@@ -625,7 +626,8 @@ static int64_t chunk_rays(const lpc_handle *h)
 // (it runs empty) when more children are kept, and the host re-runs it.
 static int64_t ds_cap(const lpc_handle *h)
 {
-    return std::max<int64_t>(0, std::min<int64_t>({h->resort_min - 1, chunk_rays(h), (int64_t)LPC_Q_MAX_PACKETS * 64}));
+    const int64_t cap = std::min<int64_t>({h->knobs.resort_min - 1, chunk_rays(h), (int64_t)LPC_Q_MAX_PACKETS * 64});
+    return std::max<int64_t>(0, cap);
 }
 
 // Workspace for a chunk of `n` rays.
@@ -634,8 +636,8 @@ static int ensure_ws(lpc_handle *h, int64_t n)
     if (n <= h->ws_rays) return 0;
     {
         const int64_t C = n;
-        RETIF(dalloc(h, h->w_key, (size_t)h->K * C * 8));
-        RETIF(dalloc(h, h->w_sc, (size_t)h->K * C * 4));
+        RETIF(dalloc(h, h->w_key, (size_t)h->scene.K * C * 8));
+        RETIF(dalloc(h, h->w_sc, (size_t)h->scene.K * C * 4));
         RETIF(dalloc(h, h->w_rs, (size_t)8 * C * 4));
         RETIF(dalloc(h, h->w_pk, (size_t)((C + 127) / 128) * sizeof(PacketRec)));
         RETIF(dalloc(h, h->d_misc, LPC_MISC_WORDS * 4));
@@ -743,7 +745,7 @@ static int spill_setup(lpc_handle *h, int64_t n, uint32_t *tmask, SpillArgs *SP)
 {
     *SP = SpillArgs{nullptr, nullptr, 0u, 0, 31, tmask, nullptr};
     if (h->prof.stats) {                // diagnostic: the fan triangles (apex valence >= 32), built once
-        if (!h->prof.d_fan.p) {
+        if (!h->scene.d_fan.p) {
             RETIF(host_vertices(h));
             std::map<std::array<uint32_t, 3>, int32_t> val;
             auto key = [&](const std::vector<float> &v, int32_t i) {
@@ -751,23 +753,25 @@ static int spill_setup(lpc_handle *h, int64_t n, uint32_t *tmask, SpillArgs *SP)
                 memcpy(k.data(), &v[4 * (size_t)i], 12);
                 return k;
             };
-            for (int32_t i = 0; i < h->M; ++i) { ++val[key(h->hv0, i)]; ++val[key(h->hv1, i)]; ++val[key(h->hv2, i)]; }
-            std::vector<uint8_t> f((size_t)h->M, 0);
-            for (int32_t i = 0; i < h->M; ++i)
-                f[(size_t)i] = val[key(h->hv0, i)] >= 32 || val[key(h->hv1, i)] >= 32 || val[key(h->hv2, i)] >= 32;
-            RETIF(dalloc(h, h->prof.d_fan, (size_t)h->M));
-            HIPCHK(h, hipMemcpy(h->prof.d_fan.p, f.data(), (size_t)h->M, hipMemcpyHostToDevice));
+            const std::vector<float> *hv = h->scene.hv;
+            const int32_t M = h->scene.M;
+            for (int32_t i = 0; i < M; ++i) { ++val[key(hv[0], i)]; ++val[key(hv[1], i)]; ++val[key(hv[2], i)]; }
+            std::vector<uint8_t> f((size_t)M, 0);
+            for (int32_t i = 0; i < M; ++i)
+                f[(size_t)i] = val[key(hv[0], i)] >= 32 || val[key(hv[1], i)] >= 32 || val[key(hv[2], i)] >= 32;
+            RETIF(dalloc(h, h->scene.d_fan, (size_t)h->scene.M));
+            HIPCHK(h, hipMemcpy(h->scene.d_fan.p, f.data(), (size_t)h->scene.M, hipMemcpyHostToDevice));
         }
-        SP->fan = (const uint8_t *)h->prof.d_fan.p;
+        SP->fan = (const uint8_t *)h->scene.d_fan.p;
     }
-    if (h->spill_budget <= 0) return 0;
-    RETIF(dalloc(h, h->w_spill, (size_t)2 * h->spill_cap * sizeof(SpillItem)));
+    if (h->knobs.spill_budget <= 0) return 0;
+    RETIF(dalloc(h, h->w_spill, (size_t)2 * h->knobs.spill_cap * sizeof(SpillItem)));
     SP->items = (SpillItem *)h->w_spill.p;
     SP->ctr = (uint32_t *)h->d_misc.p + LPC_MISC_SPILL;
-    SP->cap = (uint32_t)std::min<int64_t>(h->spill_cap, 0x7fffffff);
+    SP->cap = (uint32_t)std::min<int64_t>(h->knobs.spill_cap, 0x7fffffff);
     // no hand-over once a population fills the chip many times over (from
     // LPC_LARGE_PER_TRI rays per triangle)
-    SP->budget = n >= h->spill_large_per_tri * (int64_t)h->M ? 0 : h->spill_budget;
+    SP->budget = n >= h->knobs.spill_large_per_tri * (int64_t)h->scene.M ? 0 : h->knobs.spill_budget;
     SP->pair_shift = kSpillPairShift;
     return 0;
 }
@@ -797,9 +801,9 @@ static void spill_level_args(lpc_handle *h, const SpillArgs &SP, int l, int leve
 {
     uint32_t *misc = (uint32_t *)h->d_misc.p;
     *I = SP; *O = SP;
-    I->items = (SpillItem *)h->w_spill.p + (size_t)(l % 2) * (size_t)h->spill_cap;
+    I->items = (SpillItem *)h->w_spill.p + (size_t)(l % 2) * (size_t)h->knobs.spill_cap;
     I->ctr = misc + LPC_MISC_SPILL + l;
-    O->items = (SpillItem *)h->w_spill.p + (size_t)((l + 1) % 2) * (size_t)h->spill_cap;
+    O->items = (SpillItem *)h->w_spill.p + (size_t)((l + 1) % 2) * (size_t)h->knobs.spill_cap;
     O->ctr = misc + LPC_MISC_SPILL + l + 1;
     O->budget = l + 1 < levels ? SP.budget : 0;
 }
@@ -822,8 +826,8 @@ static int run_spill_levels(lpc_handle *h, const RaysIn &in, const float *rs, in
         // profiling counters only in the PROF instantiation (fewer live registers without)
         with_bool(stats != nullptr, [&](auto pf) {
             hipLaunchKernelGGL((k_spill<8, decltype(pf)::value>), dim3(g), dim3(64), 0, h->stream, ray, n, perm,
-                               (const Node8 *)h->d_nodes.p, (const ExactRec *)h->d_xrec.p, eps, max_ray_len, skey,
-                               scnt, stats, I, O, nd);
+                               (const Node8 *)h->scene.d_nodes.p, (const ExactRec *)h->scene.d_xrec.p, eps,
+                               max_ray_len, skey, scnt, stats, I, O, nd);
         });
     }
     HIPCHK(h, hipGetLastError());
@@ -836,7 +840,7 @@ static int run_spill_levels(lpc_handle *h, const RaysIn &in, const float *rs, in
 static int32_t q_level(const lpc_handle *h, int64_t n, bool chained)
 {
     int64_t live_runs = 0;
-    for (int32_t j = 0; j < h->K; ++j) live_runs += h->slot_run[(size_t)j] >= 0;
+    for (int32_t j = 0; j < h->scene.K; ++j) live_runs += h->scene.slot_run[(size_t)j] >= 0;
     live_runs = std::max<int64_t>(live_runs, 1);
     const int64_t npk = (n + 63) / 64;
     const int32_t g = (int32_t)std::min<int64_t>(4096, std::max<int64_t>(1, (kQTarget + npk * live_runs - 1) /
@@ -935,7 +939,7 @@ static int run_queue(lpc_handle *h, const RaysIn &in, const float *rs, int64_t n
     QueueArgs Q;
     QueueShape sh;
     RETIF(queue_args(h, n, pt, ds, &Q, &sh));
-    if (h->host_prof)
+    if (h->knobs.host_prof)
         fprintf(stderr, "[lpc host] roots: n %lld packets %lld pieces %d groups %d S %d pb %d blocks %lld rcap %lld\n",
                 (long long)n, (long long)sh.npk, (int)pt->npieces, (int)pt->ngroups, sh.rs_S, sh.rs_pb,
                 (long long)sh.rs_blocks, (long long)Q.rcap);
@@ -963,7 +967,7 @@ static int run_queue(lpc_handle *h, const RaysIn &in, const float *rs, int64_t n
     RETIF(ray_base(h, in, rs, n, &ray));
     SpillArgs SP;
     RETIF(spill_setup(h, n, tmask, &SP));
-    const unsigned grid = (unsigned)h->walk_grid;      // single-wave blocks
+    const unsigned grid = (unsigned)h->knobs.walk_grid;      // single-wave blocks
     // profiling: the launch's own start/stop timestamps (hipExtLaunchKernel), no
     // event packets between the kernels
     Event k0, k1;
@@ -977,14 +981,14 @@ static int run_queue(lpc_handle *h, const RaysIn &in, const float *rs, int64_t n
     with_bool(stats != nullptr, [&](auto pf) {
         with_bool(merged != nullptr, [&](auto mg) {
             hipExtLaunchKernelGGL((k_rootwalk<8, decltype(pf)::value, decltype(mg)::value>), dim3(grid), dim3(64), 0,
-                                  h->stream, k0, k1, 0, ray, n, perm, (const Node8 *)h->d_nodes.p,
-                                  (const ExactRec *)h->d_xrec.p, eps, max_ray_len, skey, scnt, stats, Q, SP,
+                                  h->stream, k0, k1, 0, ray, n, perm, (const Node8 *)h->scene.d_nodes.p,
+                                  (const ExactRec *)h->scene.d_xrec.p, eps, max_ray_len, skey, scnt, stats, Q, SP,
                                   ds ? ds->nd : nullptr, SA);
         });
     });
     if (*sampled) h->prof.ev_kern.emplace_back(std::move(k0), std::move(k1));
     RETIF(run_spill_levels(h, in, rs, n, perm, eps, max_ray_len, skey, scnt, stats, SP, ds ? ds->nd : nullptr));
-    if (h->host_prof >= 2) {                          // diagnostic: this launch's hand-over queue lengths
+    if (h->knobs.host_prof >= 2) {                          // diagnostic: this launch's hand-over queue lengths
         uint32_t q[8] = {0};
         HIPCHK(h, hipStreamSynchronize(h->stream));
         HIPCHK(h, hipMemcpy(q, (uint32_t *)h->d_misc.p + LPC_MISC_SPILL, sizeof(q), hipMemcpyDeviceToHost));
@@ -1066,7 +1070,7 @@ static int run_intersect(lpc_handle *h, const IsectIn &a, IsectOut *out)
     int32_t *scnt = (int32_t *)h->w_sc.p;
     uint32_t *misc = (uint32_t *)h->d_misc.p;
     SlotInit SI;
-    SI.K = h->K; SI.live = (const int32_t *)h->d_live.p; SI.max_ray_len = max_ray_len;
+    SI.K = h->scene.K; SI.live = (const int32_t *)h->scene.d_live.p; SI.max_ray_len = max_ray_len;
     SI.skey = skey; SI.scnt = scnt; SI.misc = misc;
     SI.acc = h->acc_pending ? (DevAcc *)h->d_acc.p : nullptr;
     SI.m_total = (unsigned long long)h->acc_pending_total;
@@ -1078,7 +1082,7 @@ static int run_intersect(lpc_handle *h, const IsectIn &a, IsectOut *out)
     const bool chained_pop = traced && h->pop.traced;
     // a chained population keeps its parents' order, except a large one
     // (LPC_RESORT_MIN): after many generations that order has lost its coherence
-    const bool sorted = n >= kSortMin && (!chained_pop || (!ds && n >= h->resort_min));
+    const bool sorted = n >= kSortMin && (!chained_pop || (!ds && n >= h->knobs.resort_min));
     // the slot reset rides on k_raykey when it runs before everything that reads misc
     const bool fold_init = sorted && n >= LPC_MISC_WORDS;
     // Traced iterations (k_shade_stage) leave every slot they read in the clean
@@ -1089,13 +1093,13 @@ static int run_intersect(lpc_handle *h, const IsectIn &a, IsectOut *out)
     // of a trace's chained populations; "emitted" = the trace's first population,
     // whatever the export mode; the drop-in kernels (lpc_intersect,
     // lpc_bounce_host: no trace population) are never culled.  0: off.
-    const bool half = a.trace && h->half == 3 && !h->pop.emitted;
+    const bool half = a.trace && h->knobs.half == 3 && !h->pop.emitted;
     const bool restore = traced;
     const bool clean = restore && h->slots_clean && h->slots_mrl == max_ray_len;
     // written-slot masks: kept by every flush of this launch, read by its
     // k_shade_stage (restore path only; a mask bit may be stale, never missing:
     // the masks are cleared with the slots, and only the restore path reads them)
-    uint32_t *const tmask = (restore && h->K <= 32) ? (uint32_t *)h->w_tm.p : nullptr;
+    uint32_t *const tmask = (restore && h->scene.K <= 32) ? (uint32_t *)h->w_tm.p : nullptr;
     out->tmask = tmask;
     const bool misc_clean = restore && h->misc_clean;
     h->slots_clean = h->misc_clean = false;
@@ -1122,6 +1126,7 @@ static int run_intersect(lpc_handle *h, const IsectIn &a, IsectOut *out)
     const int32_t *perm = nullptr;
     const float *rs = nullptr;
     bool roots_done = false;                    // k_gather_roots wrote the root items
+    const float *blo = h->scene.box_lo, *bsc = h->scene.box_scale;     // the coherence key's box
     if (sorted) {
         // coherence order: rays of one wave share origin cell and direction
         // (key [scene-box origin cell | direction], k_raykey), gathered from the
@@ -1131,32 +1136,30 @@ static int run_intersect(lpc_handle *h, const IsectIn &a, IsectOut *out)
         int32_t *vin = (int32_t *)(kout + C), *vout = vin + C;
         // the emitted rays' varying key bits (set_rays)
         int b0 = 0, b1 = 32;
-        if (traced && h->pop.emitted) { b0 = h->init_key_lo; b1 = h->init_key_hi; }
+        if (traced && h->pop.emitted) { b0 = h->emitted.init_key_lo; b1 = h->emitted.init_key_hi; }
         const int nbits = b1 - b0;
-        if (traced && h->pop.emitted && h->init_bsort && nbits >= 1 && nbits <= 16 && n >= LPC_MISC_WORDS) {
+        if (traced && h->pop.emitted && h->emitted.init_bsort && nbits >= 1 && nbits <= 16 && n >= LPC_MISC_WORDS) {
             // counting sort (MSD, two 8-bit digits, stable), then the gather
             const int hb = std::min(nbits, LPC_BS_HB), lb = nbits - hb;
             const int64_t nblk = (n + LPC_BS_RPB - 1) / LPC_BS_RPB;
             uint32_t *hist = (uint32_t *)h->w_bhist.p, *tot = hist + (size_t)LPC_BS_ND * nblk;
             uint32_t *bst = tot + LPC_BS_ND;
-            hipLaunchKernelGGL(k_bkey, dim3((unsigned)nblk), dim3(LPC_BS_T), 0, h->stream, in, n, h->box_lo[0],
-                               h->box_lo[1], h->box_lo[2], h->box_scale[0], h->box_scale[1], h->box_scale[2], kin,
-                               (float4 *)h->w_aos.p, SIk, b0, lb, hb, hist, nblk);
+            hipLaunchKernelGGL(k_bkey, dim3((unsigned)nblk), dim3(LPC_BS_T), 0, h->stream, in, n, blo[0], blo[1],
+                               blo[2], bsc[0], bsc[1], bsc[2], kin, (float4 *)h->w_aos.p, SIk, b0, lb, hb, hist, nblk);
             hipLaunchKernelGGL(k_bprefix, dim3(1u << hb), dim3(256), 0, h->stream, hist, nblk, tot);
             hipLaunchKernelGGL(k_bscatter, dim3((unsigned)nblk), dim3(LPC_BS_T), 0, h->stream, (const uint32_t *)kin,
                                n, b0, lb, hb, (const uint32_t *)hist, nblk, (const uint32_t *)tot, bst,
                                (uint8_t *)kout, vin, vout);
             if (lb > 0)
                 hipLaunchKernelGGL(k_bsort2, dim3(1u << hb, LPC_BS_MAXB / LPC_BS_RPB), dim3(LPC_BS_T), 0, h->stream,
-                                   (const uint8_t *)kout,
-                                   (const int32_t *)vin, lb, (const uint32_t *)bst, vout);
+                                   (const uint8_t *)kout, (const int32_t *)vin, lb, (const uint32_t *)bst, vout);
         } else {
             // a re-sorted chained population: the key (5-D Morton) spans its own box
             // (k_stage_move of the iteration that made it), not the scene's
             const uint32_t *pbox = (traced && chained_pop && h->pop.pbox_ok) ? (const uint32_t *)h->d_pbox.p : nullptr;
-            hipLaunchKernelGGL(k_raykey, dim3(grid1(n)), dim3(256), 0, h->stream, in, n, h->box_lo[0], h->box_lo[1],
-                               h->box_lo[2], h->box_scale[0], h->box_scale[1], h->box_scale[2], kin, vin,
-                               (float4 *)h->w_aos.p, SIk, pbox, pbox ? kKeyObits : 5, pbox ? 1 : 0);
+            hipLaunchKernelGGL(k_raykey, dim3(grid1(n)), dim3(256), 0, h->stream, in, n, blo[0], blo[1], blo[2], bsc[0],
+                               bsc[1], bsc[2], kin, vin, (float4 *)h->w_aos.p, SIk, pbox, pbox ? kKeyObits : 5,
+                               pbox ? 1 : 0);
             size_t tb = h->sort_tmp_bytes;
             if (n >= kOnesweepMin)          // large populations: onesweep (one pass per 8 key bits)
                 HIPCHK(h, rocprim::radix_sort_pairs<RaySortOnesweep>(h->w_sort_tmp.p, tb, kin, kout, vin, vout,
@@ -1215,7 +1218,7 @@ static int run_intersect(lpc_handle *h, const IsectIn &a, IsectOut *out)
     // launched after the hierarchy stage's kernels (the host reaches k_roots_s /
     // k_rootwalk sooner).  One stream per trace keeps several traces in flight
     // from interleaving fork / join events
-    const bool merge_try = h->sliver_merge >= 0 && n >= h->sliver_merge && nsp > 0 && pt->npieces > 0;
+    const bool merge_try = h->knobs.sliver_merge >= 0 && n >= h->knobs.sliver_merge && nsp > 0 && pt->npieces > 0;
     const bool side = !merge_try && nsp > 0 && side_stream(h);
     hipStream_t ss = h->stream;
     if (side) {
@@ -1226,7 +1229,7 @@ static int run_intersect(lpc_handle *h, const IsectIn &a, IsectOut *out)
         SliverArgs A;
         memset(&A, 0, sizeof(A));
         A.R = in; A.rs = rs; A.n = n; A.perm = perm; A.pk = (const PacketRec *)h->w_pk.p;
-        A.srec = (const SliverRec *)h->d_srec.p; A.pieces = (const Piece *)pt->spieces.p; A.nsp = nsp;
+        A.srec = (const SliverRec *)h->scene.d_srec.p; A.pieces = (const Piece *)pt->spieces.p; A.nsp = nsp;
         A.ppw = (int)ppw; A.eps = eps; A.max_ray_len = max_ray_len; A.dmax = dmax;
         A.skey = skey; A.scnt = scnt; A.stats = stats; A.nd = nd_dev; A.dm2d = dm2_dev; A.tmask = tmask;
         return A;
@@ -1261,14 +1264,14 @@ static int run_intersect(lpc_handle *h, const IsectIn &a, IsectOut *out)
         }
         if (!h->prof.light || out->sampled) {
             h->prof.launches += 1;
-            h->prof.pairs += n * (int64_t)h->M;
+            h->prof.pairs += n * (int64_t)h->scene.M;
         }
     }
     if (side) RETIF(launch_slivers());
     if (side) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_side[1], 0));
     if (a.st_user) {
-        hipLaunchKernelGGL(k_slot_export, dim3(grid1(n)), dim3(256), 0, h->stream, n, h->K,
-                           (const int32_t *)h->d_live.p, (const unsigned long long *)skey,
+        hipLaunchKernelGGL(k_slot_export, dim3(grid1(n)), dim3(256), 0, h->stream, n, h->scene.K,
+                           (const int32_t *)h->scene.d_live.p, (const unsigned long long *)skey,
                            (const int32_t *)scnt, a.st_user, a.si_user, a.sc_user, 1);
     }
     HIPCHK(h, hipGetLastError());
@@ -1279,11 +1282,11 @@ static ShadeArgs shade_args(lpc_handle *h, const RaysIn &in, const int32_t *meas
                             float ior_env, bool extra)
 {
     ShadeArgs A;
-    A.in = in; A.meas_in = meas_in; A.n = n; A.K = h->K;
+    A.in = in; A.meas_in = meas_in; A.n = n; A.K = h->scene.K;
     A.skey = (const unsigned long long *)h->w_key.p; A.sc = (const int32_t *)h->w_sc.p;
-    A.mat_type = (const int32_t *)h->d_mat.p; A.ior = (const float *)h->d_ior.p;
-    A.refl = (const float *)h->d_refl.p; A.diss = (const float *)h->d_diss.p;
-    A.verts = (const float *)h->d_verts.p;
+    A.mat_type = (const int32_t *)h->scene.d_mat.p; A.ior = (const float *)h->scene.d_ior.p;
+    A.refl = (const float *)h->scene.d_refl.p; A.diss = (const float *)h->scene.d_diss.p;
+    A.verts = (const float *)h->scene.d_verts.p;
     A.max_ray_len = max_ray_len; A.ior_env = ior_env;
     A.o = shade_ptrs(h, extra);
     return A;
@@ -1293,21 +1296,45 @@ static int run_shade(lpc_handle *h, const RaysIn &in, const int32_t *meas_in, in
                      float max_ray_len, float ior_env, bool extra)
 {
     const ShadeArgs A = shade_args(h, in, meas_in, n, max_ray_len, ior_env, extra);
-    with_ku(h->K, [&](auto ku) {
+    with_ku(h->scene.K, [&](auto ku) {
         hipLaunchKernelGGL(k_shade<decltype(ku)::value>, dim3(grid1(n)), dim3(256), 0, h->stream, A);
     });
     HIPCHK(h, hipGetLastError());
     return 0;
 }
 
+// The gates: of every entry point that computes on the scene, and of those that
+// trace the emitted rays (they go with their scene).
+static int need_scene(lpc_handle *h) { return h->scene.ready ? 0 : set_err(h, LPC_E_STATE, "no scene uploaded"); }
+static int need_rays(lpc_handle *h, const char *who)
+{
+    RETIF(need_scene(h));
+    return h->emitted.ready ? 0 : set_err(h, LPC_E_STATE, std::string(who) + " before trace_set_rays");
+}
+
+// The old scene goes: what depends on it is marked in this one place.  The
+// buffers stay (dalloc grows only); scene_publish ends the filling.
+static void scene_invalidate(lpc_handle *h)
+{
+    h->scene.ready = false;
+    h->scene.ptabs.clear();
+    h->scene.d_fan.reset();             // profiling flags of the previous scene
+    h->emitted = Emitted{};
+    h->ws_rays = 0;                     // K may change
+    ++h->scene_gen;                     // staged batches' scans keyed to the old box are redone when traced
+}
+static int scene_publish(lpc_handle *h) { h->scene.ready = true; return 0; }   // the only place
+
 // If |D| of any upcoming ray exceeds the filter's Dcap, rebuild the filter
-// records without the tiny-triangle culling (Dcap = inf).
+// records without the tiny-triangle culling (Dcap = inf).  A trace may be running:
+// the rebuilt scene keeps its rays and workspace, a failed rebuild leaves neither.
 static int check_dcap(lpc_handle *h, double dmax2)
 {
-    if (dmax2 <= h->dcap * h->dcap * (1.0 - 1e-6)) return 0;
-    h->dcap = INFINITY;
+    if (dmax2 <= h->scene.dcap * h->scene.dcap * (1.0 - 1e-6)) return 0;
+    h->scene.dcap = INFINITY;
     h->dcap_rebuilt = true;
-    return build_records(h);
+    if (const int rc = build_records(h)) { scene_invalidate(h); return rc; }
+    return scene_publish(h);
 }
 
 extern "C" {
@@ -1366,27 +1393,25 @@ int lpc_open(int device, lpc_handle **out)
     if (hipMemset(h->d_acc.p, 0, sizeof(DevAcc)) != hipSuccess ||   // counters start empty (qerr 0)
         hipMemset(h->d_ctl.p, 0, sizeof(IterCtl)) != hipSuccess)
         return set_err(nullptr, LPC_E_HIP, "counter init");
-    // size switches and test hooks (results do not depend on them; DESIGN.md
-    // section 5): the tests drive the re-sort, the merged sliver units, the work
-    // hand-over and its queue overflow, chunked iterations and a filter-record
-    // rebuild inside a trace at small sizes
+    // results do not depend on the knobs: the tests drive the re-sort, the merged sliver
+    // units, the hand-over and its queue overflow, chunked iterations and a records rebuild in a trace at small sizes
     auto env_int = [](const char *k, int64_t dflt) -> int64_t {
         const char *v = getenv(k);
         return (v && *v) ? strtoll(v, nullptr, 10) : dflt;
     };
-    h->half = env_int("LPC_HALF", h->half) == 0 ? 0 : 3;
-    h->chunk = std::max<int64_t>(0, env_int("LPC_CHUNK", h->chunk));
-    h->resort_min = std::max<int64_t>(1, env_int("LPC_RESORT_MIN", h->resort_min));
-    h->sliver_merge = env_int("LPC_SLIVER_MERGE", h->sliver_merge);
-    h->walk_grid = std::min<int64_t>(std::max<int64_t>(env_int("LPC_WALK_GRID", h->walk_grid), 64), 1 << 22);
-    h->spec = env_int("LPC_SPEC", h->spec) != 0;
-    h->dcap_init = (double)env_int("LPC_DCAP_MILLI", 16000) / 1000.0;
-    h->spill_budget = (int)env_int("LPC_BUDGET", h->spill_budget);
-    h->spill_large_per_tri = env_int("LPC_LARGE_PER_TRI", h->spill_large_per_tri);
-    h->spill_cap = std::max<int64_t>(env_int("LPC_SPILL_CAP", h->spill_cap), 64);
-    h->host_prof = (int)env_int("LPC_HOSTPROF", 0);
-    h->stage.stage_mode =
-        (int)std::min<int64_t>(2, std::max<int64_t>(0, env_int("LPC_STAGE_MODE", h->stage.stage_mode)));
+    Knobs &k = h->knobs;
+    k.half = env_int("LPC_HALF", k.half) == 0 ? 0 : 3;
+    k.chunk = std::max<int64_t>(0, env_int("LPC_CHUNK", k.chunk));
+    k.resort_min = std::max<int64_t>(1, env_int("LPC_RESORT_MIN", k.resort_min));
+    k.sliver_merge = env_int("LPC_SLIVER_MERGE", k.sliver_merge);
+    k.walk_grid = std::min<int64_t>(std::max<int64_t>(env_int("LPC_WALK_GRID", k.walk_grid), 64), 1 << 22);
+    k.spec = env_int("LPC_SPEC", k.spec) != 0;
+    k.dcap_init = (double)env_int("LPC_DCAP_MILLI", 16000) / 1000.0;
+    k.spill_budget = (int)env_int("LPC_BUDGET", k.spill_budget);
+    k.spill_large_per_tri = env_int("LPC_LARGE_PER_TRI", k.spill_large_per_tri);
+    k.spill_cap = std::max<int64_t>(env_int("LPC_SPILL_CAP", k.spill_cap), 64);
+    k.host_prof = (int)env_int("LPC_HOSTPROF", 0);
+    k.stage_mode = (int)std::min<int64_t>(2, std::max<int64_t>(0, env_int("LPC_STAGE_MODE", k.stage_mode)));
     if (h->acc_map.alloc(kAccRing * sizeof(DevAcc), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
         hipHostGetDevicePointer((void **)&h->acc_map_dev, h->acc_map, 0) != hipSuccess) {
         h->acc_map.reset();                          // counters then come by copy + stream sync
@@ -1438,77 +1463,71 @@ int lpc_scene_upload(lpc_handle *h, int32_t tri_count, const float *v0, const fl
 {
     if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
     RETIF(settle(h));                   // a trace still running (lpc_trace_iterate / _run_async)
-    if (tri_count <= 0 || mesh_count <= 0 || !v0 || !v1 || !v2 || !mesh_id || !mat_type || !ior ||
-        !refl || !diss)
+    // validation, on locals: a refused upload leaves the handle as it was
+    if (tri_count <= 0 || mesh_count <= 0 || !v0 || !v1 || !v2 || !mesh_id || !mat_type || !ior || !refl || !diss)
         return set_err(h, LPC_E_ARG, "scene needs >= 1 triangle, >= 1 mesh and all tables");
     // the walk's sparse exact-test pairs hold a triangle index in 26 bits (and root
     // items node ids in 28, LPC_Q_MAX_NODES)
-    if (tri_count >= (1 << 26))
-        return set_err(h, LPC_E_ARG, "scene has too many triangles (limit 2^26 - 1)");
+    if (tri_count >= (1 << 26)) return set_err(h, LPC_E_ARG, "scene has too many triangles (limit 2^26 - 1)");
     // the root items carry a mesh's scratch slot in 12 bits (q_item)
     if (mesh_count > LPC_Q_MAX_SLOTS + 1)
         return set_err(h, LPC_E_ARG, "scene has too many meshes (limit " + std::to_string(LPC_Q_MAX_SLOTS + 1) + ")");
-    const double tu0 = h->host_prof ? host_us() : 0.0;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    ++h->scene_gen;                     // staged batches' scans keyed to the old box are redone when traced
+    const double tu0 = h->knobs.host_prof ? host_us() : 0.0;
     const int32_t M = tri_count, K = mesh_count;
     for (int32_t i = 0; i < M; ++i)
         if (mesh_id[i] < 0 || mesh_id[i] >= K)
             return set_err(h, LPC_E_ARG, "mesh_id[" + std::to_string(i) + "] out of range");
-    h->M = M; h->K = K;
-    h->prof.d_fan.reset();                          // profiling flags of the previous scene
-    // the rows go to the device as they are (the vertex and exact records are
-    // built there); the host reads the caller's arrays during this call and keeps
-    // no copy (host_vertices fetches one for a later rebuild)
-    h->hv0.clear(); h->hv1.clear(); h->hv2.clear();
-    h->src_v[0] = v0; h->src_v[1] = v1; h->src_v[2] = v2;
-    RETIF(dalloc(h, h->d_raw, (size_t)M * 48));
-    for (int k = 0; k < 3; ++k)
-        HIPCHK(h, hipMemcpyAsync((float *)h->d_raw.p + (size_t)k * 4 * M, k == 0 ? v0 : k == 1 ? v1 : v2,
-                                 (size_t)M * 16, hipMemcpyHostToDevice, h->stream));
     // runs of equal mesh_id and the slot each one flushes into (.cl:260-265, 286)
-    h->run_lo.clear(); h->run_hi.clear();
+    std::vector<int32_t> run_lo, run_hi, slot_run((size_t)K, -1);
     for (int32_t i = 0; i < M; ++i) {
-        if (i == 0 || mesh_id[i] != mesh_id[i - 1]) { h->run_lo.push_back(i); h->run_hi.push_back(i + 1); }
-        else h->run_hi.back() = i + 1;
+        if (i == 0 || mesh_id[i] != mesh_id[i - 1]) { run_lo.push_back(i); run_hi.push_back(i + 1); }
+        else run_hi.back() = i + 1;
     }
-    const size_t nr = h->run_lo.size();
-    h->slot_run.assign((size_t)K, -1);
-    for (size_t r = 0; r < nr; ++r) {
-        int32_t slot = (r + 1 < nr) ? mesh_id[h->run_lo[r + 1]] - 1 : mesh_id[h->run_lo[r]];
+    for (size_t r = 0, nr = run_lo.size(); r < nr; ++r) {
+        int32_t slot = (r + 1 < nr) ? mesh_id[run_lo[r + 1]] - 1 : mesh_id[run_lo[r]];
         if (slot < 0)
             return set_err(h, LPC_E_ARG, "mesh_id sequence writes below slot 0 (reference would "
                                          "corrupt another ray's scratch); mesh ids must not decrease to 0");
-        h->slot_run[slot] = (int32_t)r;   // a later run overwrites, as the sequential loop does
+        slot_run[slot] = (int32_t)r;      // a later run overwrites, as the sequential loop does
     }
-    {
-        std::vector<int32_t> live((size_t)K);
-        for (int32_t j = 0; j < K; ++j) live[(size_t)j] = h->slot_run[(size_t)j] >= 0;
-        RETIF(dalloc(h, h->d_live, (size_t)K * 4));
-        HIPCHK(h, hipMemcpy(h->d_live.p, live.data(), (size_t)K * 4, hipMemcpyHostToDevice));
-    }
-    h->meas_meshes.clear();
-    for (int32_t j = 0; j < K; ++j) if (mat_type[j] == 3) h->meas_meshes.push_back(j);
+    // the old scene goes; until scene_publish below there is none
+    scene_invalidate(h);
+    Scene &sc = h->scene;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    sc.M = M; sc.K = K; sc.dcap = h->knobs.dcap_init;
+    sc.run_lo.swap(run_lo); sc.run_hi.swap(run_hi); sc.slot_run.swap(slot_run);
+    // the rows go to the device as they are (the vertex and exact records are
+    // built there); the host reads the caller's arrays during this call and keeps
+    // no copy (host_vertices fetches one for a later rebuild)
+    for (auto &v : sc.hv) v.clear();
+    RETIF(dalloc(h, sc.d_raw, (size_t)M * 48));
+    for (int k = 0; k < 3; ++k)
+        HIPCHK(h, hipMemcpyAsync((float *)sc.d_raw.p + (size_t)k * 4 * M, k == 0 ? v0 : k == 1 ? v1 : v2,
+                                 (size_t)M * 16, hipMemcpyHostToDevice, h->stream));
+    std::vector<int32_t> live((size_t)K);
+    for (int32_t j = 0; j < K; ++j) live[(size_t)j] = sc.slot_run[(size_t)j] >= 0;
+    RETIF(dalloc(h, sc.d_live, (size_t)K * 4));
+    HIPCHK(h, hipMemcpy(sc.d_live.p, live.data(), (size_t)K * 4, hipMemcpyHostToDevice));
+    sc.meas_meshes.clear();
+    for (int32_t j = 0; j < K; ++j) if (mat_type[j] == 3) sc.meas_meshes.push_back(j);
     // passive materials: the children of a ray never carry more power than it
     // (refractive: R, T = 1 - R in [0, 1] for finite positive indices,
     // .cl:313-326; mirror: P R with 0 <= R <= 1, .cl:443 -- a negative R flips the
     // sign, so a population's summed power could grow; dissipation only
     // attenuates, .cl:385-394)
-    h->mat_passive = true;
+    sc.mat_passive = true;
     for (int32_t j = 0; j < K; ++j) {
         if ((mat_type[j] == 0 || mat_type[j] == 4) && !(ior[j] > 0.0f && std::isfinite(ior[j])))
-            h->mat_passive = false;
-        if (mat_type[j] == 1 && !(refl[j] >= 0.0f && refl[j] <= 1.0f)) h->mat_passive = false;
+            sc.mat_passive = false;
+        if (mat_type[j] == 1 && !(refl[j] >= 0.0f && refl[j] <= 1.0f)) sc.mat_passive = false;
     }
     // vertices (the hit triangle's normal in the shading), from the rows on the device
-    RETIF(dalloc(h, h->d_verts, (size_t)M * 36));
-    {
-        const float4 *raw = (const float4 *)h->d_raw.p;
-        hipLaunchKernelGGL(k_vertex_rows, dim3(grid1(M)), dim3(256), 0, h->stream, (int64_t)M, raw, raw + M,
-                           raw + 2 * (size_t)M, (float *)h->d_verts.p);
-        HIPCHK(h, hipGetLastError());
-    }
+    RETIF(dalloc(h, sc.d_verts, (size_t)M * 36));
+    const float4 *raw = (const float4 *)sc.d_raw.p;
+    hipLaunchKernelGGL(k_vertex_rows, dim3(grid1(M)), dim3(256), 0, h->stream, (int64_t)M, raw, raw + M,
+                       raw + 2 * (size_t)M, (float *)sc.d_verts.p);
+    HIPCHK(h, hipGetLastError());
     {   // scene box for the ray coherence key
         float lo3[3] = {INFINITY, INFINITY, INFINITY}, hi3[3] = {-INFINITY, -INFINITY, -INFINITY};
         for (const float *vs : {v0, v1, v2})
@@ -1520,32 +1539,24 @@ int lpc_scene_upload(lpc_handle *h, int32_t tri_count, const float *v0, const fl
         double diag2 = 0.0;
         for (int k = 0; k < 3; ++k) {
             const float ext = hi3[k] - lo3[k];
-            h->box_lo[k] = std::isfinite(lo3[k]) ? lo3[k] : 0.0f;
-            h->box_scale[k] = (std::isfinite(ext) && ext > 0.0f) ? 32.0f / ext : 1.0f;
+            sc.box_lo[k] = std::isfinite(lo3[k]) ? lo3[k] : 0.0f;
+            sc.box_scale[k] = (std::isfinite(ext) && ext > 0.0f) ? 32.0f / ext : 1.0f;
             if (std::isfinite(ext)) diag2 += (double)ext * ext;
         }
-        h->scene_scale = diag2 > 0.0 ? 0.5 * sqrt(diag2) : 1.0;
+        sc.scene_scale = diag2 > 0.0 ? 0.5 * sqrt(diag2) : 1.0;
     }
-    h->dcap = h->dcap_init;
-    const double tu1 = h->host_prof ? host_us() : 0.0;
-    const int brc = build_records(h);
-    h->src_v[0] = h->src_v[1] = h->src_v[2] = nullptr;     // the caller's arrays are theirs again
-    RETIF(brc);
-    const double tu2 = h->host_prof ? host_us() : 0.0;
-    RETIF(dalloc(h, h->d_mat, (size_t)K * 4));
-    RETIF(dalloc(h, h->d_ior, (size_t)K * 4));
-    RETIF(dalloc(h, h->d_refl, (size_t)K * 4));
-    RETIF(dalloc(h, h->d_diss, (size_t)K * 4));
-    HIPCHK(h, hipMemcpy(h->d_mat.p, mat_type, (size_t)K * 4, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(h->d_ior.p, ior, (size_t)K * 4, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(h->d_refl.p, refl, (size_t)K * 4, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(h->d_diss.p, diss, (size_t)K * 4, hipMemcpyHostToDevice));
-    h->ws_rays = 0;   // K may have changed
-    h->traced_ready = false;
-    if (h->host_prof)
+    const double tu1 = h->knobs.host_prof ? host_us() : 0.0;
+    const float *const rows[3] = {v0, v1, v2};
+    RETIF(build_records(h, rows));
+    const double tu2 = h->knobs.host_prof ? host_us() : 0.0;
+    const std::pair<DBuf *, const void *> tabs[] = {{&sc.d_mat, mat_type}, {&sc.d_ior, ior}, {&sc.d_refl, refl},
+                                                    {&sc.d_diss, diss}};
+    for (const auto &t : tabs) RETIF(dalloc(h, *t.first, (size_t)K * 4));
+    for (const auto &t : tabs) HIPCHK(h, hipMemcpy(t.first->p, t.second, (size_t)K * 4, hipMemcpyHostToDevice));
+    if (h->knobs.host_prof)
         fprintf(stderr, "[lpc host] scene upload: tables %.1f us, records %.1f us, device copies %.1f us\n", tu1 - tu0,
                 tu2 - tu1, host_us() - tu2);
-    return 0;
+    return scene_publish(h);
 }
 
 // The process's host worker threads (host_threads() - 1 of them beside the
@@ -1695,7 +1706,7 @@ int lpc_bounce_host(lpc_handle *h, int64_t n, const float *origin4, const float 
 {
     if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
     RETIF(settle(h));                   // a trace still running (lpc_trace_iterate / _run_async)
-    if (!h->M) return set_err(h, LPC_E_STATE, "no scene uploaded");
+    RETIF(need_scene(h));
     if (n < 0 || !origin4 || !dir4 || !pow || !meas || !prev_mid || !dest4 || !isect_mid ||
         !r_dir4 || !r_pow || !r_meas || !t_dir4 || !t_pow || !t_meas)
         return set_err(h, LPC_E_ARG, "bounce_host: missing buffer");
@@ -1759,7 +1770,7 @@ int lpc_intersect(lpc_handle *h, int64_t n, const float *dev_origin4, const floa
 {
     if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
     RETIF(settle(h));                   // a trace still running (lpc_trace_iterate / _run_async)
-    if (!h->M) return set_err(h, LPC_E_STATE, "no scene uploaded");
+    RETIF(need_scene(h));
     if (n < 0 || !dev_origin4 || !dev_dir4 || !dev_tmin || !dev_cnt || !dev_itmp)
         return set_err(h, LPC_E_ARG, "intersect: missing buffer");
     if (n == 0) return 0;
@@ -1778,8 +1789,8 @@ int lpc_intersect(lpc_handle *h, int64_t n, const float *dev_origin4, const floa
         in.ox = s; in.oy = s + Cw; in.oz = s + 2 * Cw; in.dx = s + 3 * Cw; in.dy = s + 4 * Cw;
         in.dz = s + 5 * Cw; in.pw = nullptr; in.pmid = nullptr;
         IsectOut io;
-        RETIF(run_intersect(h, IsectIn{in, nc, max_ray_len, INFINITY, dev_tmin + base * h->K, dev_itmp + base * h->K,
-                                       dev_cnt + base * h->K}, &io));
+        const int64_t b = base * h->scene.K;
+        RETIF(run_intersect(h, IsectIn{in, nc, max_ray_len, INFINITY, dev_tmin + b, dev_itmp + b, dev_cnt + b}, &io));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     RETIF(check_qerr(h));
@@ -1796,7 +1807,7 @@ int lpc_intersect_postproc(lpc_handle *h, int64_t n, const float *dev_origin4,
 {
     if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
     RETIF(settle(h));                   // a trace still running (lpc_trace_iterate / _run_async)
-    if (!h->M) return set_err(h, LPC_E_STATE, "no scene uploaded");
+    RETIF(need_scene(h));
     if (n < 0 || !dev_origin4 || !dev_dir4 || !dev_dest4 || !dev_prev_mid || !dev_n1_mid ||
         !dev_n2_mid || !dev_entering || !dev_isect_mid || !dev_isect_idx || !dev_tmin ||
         !dev_cnt || !dev_itmp)
@@ -1804,13 +1815,13 @@ int lpc_intersect_postproc(lpc_handle *h, int64_t n, const float *dev_origin4,
     if (n == 0) return 0;
     HIPCHK(h, hipSetDevice(h->device));
     PostprocAosArgs A;
-    A.n = n; A.K = h->K;
+    A.n = n; A.K = h->scene.K;
     A.origin = (const float4 *)dev_origin4; A.dir = (const float4 *)dev_dir4;
     A.dest = (float4 *)dev_dest4; A.prev_mid = dev_prev_mid;
     A.n1 = dev_n1_mid; A.n2 = dev_n2_mid; A.entering = dev_entering;
     A.imid = dev_isect_mid; A.iidx = dev_isect_idx;
     A.tmin = dev_tmin; A.cnt = dev_cnt; A.itmp = dev_itmp;
-    A.mat_type = (const int32_t *)h->d_mat.p; A.max_ray_len = max_ray_len;
+    A.mat_type = (const int32_t *)h->scene.d_mat.p; A.max_ray_len = max_ray_len;
     hipLaunchKernelGGL(k_postproc_aos, dim3(grid1(n)), dim3(256), 0, h->stream, A);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1828,7 +1839,7 @@ int lpc_reflect_refract_rays(lpc_handle *h, int64_t n, const float *dev_origin4,
 {
     if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
     RETIF(settle(h));                   // a trace still running (lpc_trace_iterate / _run_async)
-    if (!h->M) return set_err(h, LPC_E_STATE, "no scene uploaded");
+    RETIF(need_scene(h));
     if (n < 0 || !dev_origin4 || !dev_dest4 || !dev_dir4 || !dev_pow || !dev_meas ||
         !dev_n1_mid || !dev_n2_mid || !dev_r_origin4 || !dev_r_dir4 || !dev_r_pow ||
         !dev_r_meas || !dev_t_origin4 || !dev_t_dir4 || !dev_t_pow || !dev_t_meas ||
@@ -1844,9 +1855,9 @@ int lpc_reflect_refract_rays(lpc_handle *h, int64_t n, const float *dev_origin4,
     A.r_origin = (float4 *)dev_r_origin4; A.r_dir = (float4 *)dev_r_dir4;
     A.t_origin = (float4 *)dev_t_origin4; A.t_dir = (float4 *)dev_t_dir4;
     A.r_pow = dev_r_pow; A.t_pow = dev_t_pow; A.r_meas = dev_r_meas; A.t_meas = dev_t_meas;
-    A.mat_type = (const int32_t *)h->d_mat.p; A.ior = (const float *)h->d_ior.p;
-    A.refl = (const float *)h->d_refl.p; A.diss = (const float *)h->d_diss.p;
-    A.verts = (const float *)h->d_verts.p; A.ior_env = ior_env;
+    A.mat_type = (const int32_t *)h->scene.d_mat.p; A.ior = (const float *)h->scene.d_ior.p;
+    A.refl = (const float *)h->scene.d_refl.p; A.diss = (const float *)h->scene.d_diss.p;
+    A.verts = (const float *)h->scene.d_verts.p; A.ior_env = ior_env;
     hipLaunchKernelGGL(k_fresnel_aos, dim3(grid1(n)), dim3(256), 0, h->stream, A);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1859,7 +1870,7 @@ int lpc_set_walk_grid(lpc_handle *h, int64_t blocks)
     if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
     if (blocks != 0 && (blocks < 64 || blocks > (1 << 22))) return set_err(h, LPC_E_ARG, "walk grid out of range");
     RETIF(settle(h));                   // a trace still running (lpc_trace_iterate / _run_async)
-    h->walk_grid = blocks ? blocks : kWalkWaves;
+    h->knobs.walk_grid = blocks ? blocks : kWalkWaves;
     return 0;
 }
 
@@ -1867,7 +1878,7 @@ int lpc_set_chunk(lpc_handle *h, int64_t rays_per_chunk)
 {
     if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
     if (rays_per_chunk < 0) return set_err(h, LPC_E_ARG, "negative chunk");
-    h->chunk = rays_per_chunk;
+    h->knobs.chunk = rays_per_chunk;
     return 0;
 }
 
@@ -1876,80 +1887,85 @@ int lpc_set_chunk(lpc_handle *h, int64_t rays_per_chunk)
 // is large: the hi-digit counts of k_raykey's key that k_ray_scan counted for
 // the key window in use.  A collimated beam's few origin cells, or a narrow
 // cone's few direction cells, go to rocPRIM (the sort is exact either way).
-static bool bsort_fits(const lpc_handle *h, int64_t n, const RayScan &S)
+static bool bsort_fits(int key_lo, int key_hi, int64_t n, const RayScan &S)
 {
-    const int nbits = h->init_key_hi - h->init_key_lo;
+    const int nbits = key_hi - key_lo;
     if (nbits < 1 || nbits > 16 || n < LPC_MISC_WORDS) return false;
     const int hb = std::min(nbits, LPC_BS_HB), lb = nbits - hb;
     if (lb == 0) return true;                              // one level: no per-bucket pass
-    const int w = h->init_key_lo + lb == 8 ? 0 : h->init_key_lo + lb == 23 ? 1 : -1;
+    const int w = key_lo + lb == 8 ? 0 : key_lo + lb == 23 ? 1 : -1;
     if (w < 0 || hb != 8) return false;                   // windows k_ray_scan did not count
     uint32_t mx = 0;
     for (int b = 0; b < 256; ++b) mx = std::max(mx, S.hist[w][b]);
     return mx <= (uint32_t)LPC_BS_MAXB;
 }
 
-static int emitted_rays(lpc_handle *h, int64_t n, const RayScan &S, float max_ray_len, float ior_env);
-
-int lpc_trace_set_rays(lpc_handle *h, int64_t n, const float *origin4, const float *dir4,
-                       const float *pow, float max_ray_len, float ior_env)
+// The analysis of n new rays against the scene's key box (k_ray_scan) on the
+// stream, read back into S (one 2 KB copy; no rays: zeros).
+static int ray_scan(lpc_handle *h, const RaysIn &in, int64_t n, DBuf &d, RayScan *S)
 {
-    if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
-    RETIF(settle(h));                   // a trace still running (lpc_trace_iterate / _run_async)
-    if (!h->M) return set_err(h, LPC_E_STATE, "no scene uploaded");
-    if (n < 0 || (n > 0 && (!origin4 || !dir4 || !pow))) return set_err(h, LPC_E_ARG, "set_rays: missing buffer");
-    HIPCHK(h, hipSetDevice(h->device));
+    const Scene &sc = h->scene;
+    memset(S, 0, sizeof(RayScan));
+    if (n <= 0) return 0;
+    RETIF(dalloc(h, d, sizeof(RayScan)));
+    HIPCHK(h, hipMemsetAsync(d.p, 0, sizeof(RayScan), h->stream));
+    hipLaunchKernelGGL(k_ray_scan, dim3((unsigned)std::min<int64_t>(grid1(n), 2048)), dim3(256), 0, h->stream, in, n,
+                       sc.box_lo[0], sc.box_lo[1], sc.box_lo[2], sc.box_scale[0], sc.box_scale[1], sc.box_scale[2],
+                       (RayScan *)d.p);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(S, d.p, sizeof(RayScan), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    RETIF(pop_reserve(h, h->I, std::max<int64_t>(n, 1)));
-    // the rays, then their analysis on the device (k_ray_scan, one 2 KB read-back)
-    RayScan S;
-    memset(&S, 0, sizeof(S));
-    if (n > 0) {
-        RETIF(upload_rays(h, h->I, n, origin4, dir4, pow, nullptr, false));
-        RETIF(dalloc(h, h->d_scan, sizeof(RayScan)));
-        HIPCHK(h, hipMemsetAsync(h->d_scan.p, 0, sizeof(RayScan), h->stream));
-        hipLaunchKernelGGL(k_ray_scan, dim3((unsigned)std::min<int64_t>(grid1(n), 2048)), dim3(256), 0, h->stream,
-                           h->I.in(), n, h->box_lo[0], h->box_lo[1], h->box_lo[2], h->box_scale[0], h->box_scale[1],
-                           h->box_scale[2], (RayScan *)h->d_scan.p);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(&S, h->d_scan.p, sizeof(RayScan), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return emitted_rays(h, n, S, max_ray_len, ior_env);
+    return 0;
 }
 
 // The emitted rays' analysis (k_ray_scan) into the trace state, as the rays in
 // I: lpc_trace_set_rays and a staged batch that becomes current.
 static int emitted_rays(lpc_handle *h, int64_t n, const RayScan &S, float max_ray_len, float ior_env)
 {
-    memcpy(&h->init_dmax2, &S.dmax2_bits, sizeof(double));
-    h->pow_nonneg = S.neg_pow == 0u;
+    Emitted E;
+    E.n_init = n; E.max_ray_len = max_ray_len; E.ior_env = ior_env;
+    memcpy(&E.init_dmax2, &S.dmax2_bits, sizeof(double));
+    E.pow_nonneg = S.neg_pow == 0u;
     // coherence key bits that can vary over these rays (k_raykey: [origin cell 15 |
     // direction 16]): a point source has one origin cell, a collimated beam one
     // direction, and the sort skips the rest
     const bool same_o = S.diff_o == 0u, same_d = S.diff_d == 0u;
-    h->init_key_lo = 0;
-    h->init_key_hi = 31;
-    if (same_o) h->init_key_hi = 16;
-    if (same_d) h->init_key_lo = 16;
-    if (same_o && same_d) { h->init_key_lo = 0; h->init_key_hi = 8; }   // one digit pass
-    h->init_bsort = bsort_fits(h, n, S);
-    RETIF(check_dcap(h, h->init_dmax2));
-    h->n_init = n;
-    h->max_ray_len = max_ray_len;
-    h->ior_env = ior_env;
-    h->traced_ready = true;
+    E.init_key_lo = 0; E.init_key_hi = 31;
+    if (same_o) E.init_key_hi = 16;
+    if (same_d) E.init_key_lo = 16;
+    if (same_o && same_d) { E.init_key_lo = 0; E.init_key_hi = 8; }   // one digit pass
+    E.init_bsort = bsort_fits(E.init_key_lo, E.init_key_hi, n, S);
+    RETIF(check_dcap(h, E.init_dmax2));             // failed: the previous record went with the scene
+    E.ready = true;
+    h->emitted = E;
     return lpc_trace_reset(h);
+}
+
+int lpc_trace_set_rays(lpc_handle *h, int64_t n, const float *origin4, const float *dir4,
+                       const float *pow, float max_ray_len, float ior_env)
+{
+    if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
+    RETIF(settle(h));                   // a trace still running (lpc_trace_iterate / _run_async)
+    RETIF(need_scene(h));
+    if (n < 0 || (n > 0 && (!origin4 || !dir4 || !pow))) return set_err(h, LPC_E_ARG, "set_rays: missing buffer");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    RETIF(pop_reserve(h, h->I, std::max<int64_t>(n, 1)));
+    if (n > 0) RETIF(upload_rays(h, h->I, n, origin4, dir4, pow, nullptr, false));
+    RayScan S;
+    RETIF(ray_scan(h, h->I.in(), n, h->d_scan, &S));
+    return emitted_rays(h, n, S, max_ray_len, ior_env);
 }
 
 int lpc_trace_reset(lpc_handle *h)
 {
     if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
-    if (!h->traced_ready) return set_err(h, LPC_E_STATE, "trace_reset before trace_set_rays");
+    RETIF(need_rays(h, "trace_reset"));
     HIPCHK(h, hipSetDevice(h->device));
     // the first iteration reads the emitted rays where set_rays put them (I is
     // never written by an iteration: no copy)
-    h->pop = PopState{h->n_init, h->init_dmax2, /*init*/ true, /*traced*/ false, /*emitted*/ true, /*pbox_ok*/ false};
+    const Emitted &E = h->emitted;
+    h->pop = PopState{E.n_init, E.init_dmax2, /*init*/ true, /*traced*/ false, /*emitted*/ true, /*pbox_ok*/ false};
     h->mp_valid = true;                             // until an iteration does not sum it
     h->m_total = 0;                             // measured record emptied (the first iteration resets the counters)
     h->m_inflight = 0;
@@ -1973,18 +1989,18 @@ int lpc_trace_reset(lpc_handle *h)
 // buffers may hold an earlier batch's emitted rays).  The main thread meanwhile
 // traces the batch before it.
 static void stage_worker(lpc_handle *h, lpc_handle::RaySlot *s, const float *origin4, const float *dir4,
-                         const float *pow, const float box_lo[3], const float box_scale[3], bool scan)
+                         const float *pow, std::array<float, 6> box, bool scan)   // box: the key box lo | scale
 {
     auto fail = [&](hipError_t e, const char *what) {
         s->rc = LPC_E_HIP;
         s->err = std::string("stage_rays: ") + what + ": " + hipGetErrorString(e);
     };
-    const double t0 = h->host_prof ? host_us() : 0.0;
+    const double t0 = h->knobs.host_prof ? host_us() : 0.0;
     hipError_t e = hipSetDevice(h->device);
     if (e != hipSuccess) { fail(e, "hipSetDevice"); return; }
     const int64_t n = s->n;
     hipStream_t cs = h->stage.cstream;
-    const int mode = h->stage.stage_mode;
+    const int mode = h->knobs.stage_mode;
     if (mode == 2) {
         // chunks: the host transposes chunk c + 1 into the pinned SoA arrays while
         // the DMAs of chunk c run (28 B per ray cross PCIe)
@@ -2038,8 +2054,7 @@ static void stage_worker(lpc_handle *h, lpc_handle::RaySlot *s, const float *ori
     if (scan) {                                     // the scene's key box is known: the analysis rides along
         if ((e = hipMemsetAsync(s->scan.p, 0, sizeof(RayScan), cs)) != hipSuccess) { fail(e, "fill"); return; }
         hipLaunchKernelGGL(k_ray_scan, dim3((unsigned)std::min<int64_t>(grid1(n), 2048)), dim3(256), 0, cs, s->P.in(),
-                           n, box_lo[0], box_lo[1], box_lo[2], box_scale[0], box_scale[1], box_scale[2],
-                           (RayScan *)s->scan.p);
+                           n, box[0], box[1], box[2], box[3], box[4], box[5], (RayScan *)s->scan.p);
         if ((e = hipGetLastError()) != hipSuccess) { fail(e, "launch"); return; }
         if ((e = hipMemcpyAsync(s->scan_host, s->scan.p, sizeof(RayScan), hipMemcpyDeviceToHost, cs)) != hipSuccess) {
             fail(e, "copy");
@@ -2047,7 +2062,7 @@ static void stage_worker(lpc_handle *h, lpc_handle::RaySlot *s, const float *ori
         }
     }
     if ((e = hipEventRecord(s->ev, cs)) != hipSuccess) fail(e, "event");
-    if (h->host_prof) {
+    if (h->knobs.host_prof) {
         const double t1 = host_us();
         (void)hipEventSynchronize(s->ev);
         fprintf(stderr, "[lpc host] stage mode %d: %lld rays, enqueued %.1f us, done %.1f us\n", mode, (long long)n,
@@ -2073,9 +2088,9 @@ int lpc_trace_stage_rays(lpc_handle *h, int64_t n, const float *origin4, const f
     // buffers (allocations synchronise; they grow only with the batch size)
     RETIF(pop_reserve(h, s.P, n));
     RETIF(dalloc(h, s.scan, sizeof(RayScan)));
-    if (h->stage.stage_mode != 2) RETIF(dalloc(h, s.aos, (size_t)n * 32));
-    const size_t pb = (size_t)n * (h->stage.stage_mode == 2 ? 28 : 36);
-    if (h->stage.stage_mode != 0 && s.pin.bytes < pb) {
+    if (h->knobs.stage_mode != 2) RETIF(dalloc(h, s.aos, (size_t)n * 32));
+    const size_t pb = (size_t)n * (h->knobs.stage_mode == 2 ? 28 : 36);
+    if (h->knobs.stage_mode != 0 && s.pin.bytes < pb) {
         if (s.pin) (void)hipStreamSynchronize(h->stage.cstream);    // its last copies end before it goes
         HIPCHK(h, s.pin.alloc(pb));
     }
@@ -2084,14 +2099,14 @@ int lpc_trace_stage_rays(lpc_handle *h, int64_t n, const float *origin4, const f
     s.ior_env = ior_env;
     s.rc = 0;
     s.err.clear();
-    s.scan_gen = h->M ? h->scene_gen : -1;      // no scene yet: the scan runs when the batch is traced
+    s.scan_gen = h->scene.ready ? h->scene_gen : -1;      // no scene yet: the scan runs when the batch is traced
     // the slot's device buffers may hold an earlier batch's emitted rays: the copy
     // stream starts after the main-stream work queued so far
     HIPCHK(h, hipEventRecord(h->stage.ev_stage, h->stream));
     HIPCHK(h, hipStreamWaitEvent(h->stage.cstream, h->stage.ev_stage, 0));
-    const float lo[3] = {h->box_lo[0], h->box_lo[1], h->box_lo[2]};
-    const float sc[3] = {h->box_scale[0], h->box_scale[1], h->box_scale[2]};
-    s.th = std::thread(stage_worker, h, &s, origin4, dir4, pow, lo, sc, s.scan_gen >= 0);
+    const float *lo = h->scene.box_lo, *sc = h->scene.box_scale;    // by value: the helper outlives this call
+    s.th = std::thread(stage_worker, h, &s, origin4, dir4, pow,
+                       std::array<float, 6>{lo[0], lo[1], lo[2], sc[0], sc[1], sc[2]}, s.scan_gen >= 0);
     ++h->stage.rs_count;
     return 0;
 }
@@ -2105,8 +2120,8 @@ int lpc_trace_run_staged_async(lpc_handle *h, int32_t max_iter, double power_thr
 {
     if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
     if (!h->stage.rs_count) return set_err(h, LPC_E_STATE, "run_staged: no batch staged (lpc_trace_stage_rays)");
-    if (!h->M) return set_err(h, LPC_E_STATE, "no scene uploaded");
-    if (mesh_power && mesh_power_cap < h->K)
+    RETIF(need_scene(h));
+    if (mesh_power && mesh_power_cap < h->scene.K)
         return set_err(h, LPC_E_ARG, "trace: mesh_power capacity below the scene's mesh count");
     if (!n_iter || (max_iter > 0 && !per_iter)) return set_err(h, LPC_E_ARG, "trace_run: null output");
     HIPCHK(h, hipSetDevice(h->device));
@@ -2119,16 +2134,8 @@ int lpc_trace_run_staged_async(lpc_handle *h, int32_t max_iter, double power_thr
     // the trace's first kernels wait for the batch on the device
     HIPCHK(h, hipEventSynchronize(s.ev));
     HIPCHK(h, hipStreamWaitEvent(h->stream, s.ev, 0));
-    if (s.scan_gen != h->scene_gen) {           // staged before this scene: its analysis now, on the stream
-        RETIF(dalloc(h, s.scan, sizeof(RayScan)));
-        HIPCHK(h, hipMemsetAsync(s.scan.p, 0, sizeof(RayScan), h->stream));
-        hipLaunchKernelGGL(k_ray_scan, dim3((unsigned)std::min<int64_t>(grid1(s.n), 2048)), dim3(256), 0, h->stream,
-                           s.P.in(), s.n, h->box_lo[0], h->box_lo[1], h->box_lo[2], h->box_scale[0],
-                           h->box_scale[1], h->box_scale[2], (RayScan *)s.scan.p);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(s.scan_host, s.scan.p, sizeof(RayScan), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
+    if (s.scan_gen != h->scene_gen)             // staged before this scene: its analysis now, on the stream
+        RETIF(ray_scan(h, s.P.in(), s.n, s.scan, s.scan_host));
     std::swap(h->I, s.P);
     RETIF(emitted_rays(h, s.n, *s.scan_host, s.max_ray_len, s.ior_env));
     return trace_run(h, max_iter, power_threshold, per_iter, n_iter, measured_count, mesh_power, mesh_power_cap,
@@ -2189,7 +2196,7 @@ int lpc_trace_run_async(lpc_handle *h, int32_t max_iter, double power_threshold,
 int lpc_trace_rerun_async(lpc_handle *h, int32_t max_iter, double power_threshold, lpc_iter_stats *per_iter,
                           int32_t *n_iter, int64_t *measured_count, double *mesh_power, int32_t mesh_power_cap)
 {
-    if (h && mesh_power && mesh_power_cap < h->K)       // before the reset: nothing changed on error
+    if (h && mesh_power && mesh_power_cap < h->scene.K)       // before the reset: nothing changed on error
         return set_err(h, LPC_E_ARG, "trace: mesh_power capacity below the scene's mesh count");
     RETIF(lpc_trace_reset(h));
     return trace_run(h, max_iter, power_threshold, per_iter, n_iter, measured_count, mesh_power, mesh_power_cap,
@@ -2400,7 +2407,7 @@ static int export_chunk(lpc_handle *h, const RaysIn &in, const ShadeOutPtrs &o, 
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->xp.ev_xready[par], h->stream));
     HIPCHK(h, hipStreamWaitEvent(h->xp.xstream, h->xp.ev_xready[par], 0));
-    const double hm = h->host_prof ? host_us() : 0.0;
+    const double hm = h->knobs.host_prof ? host_us() : 0.0;
     // the copy into the caller's pinned block: a copy kernel writing the mapped
     // block over PCIe (round 5: hipMemcpyAsync into a block stalled the host 4-15 ms
     // on the block's first asynchronous copy, whatever primed it, DESIGN.md
@@ -2418,7 +2425,7 @@ static int export_chunk(lpc_handle *h, const RaysIn &in, const ShadeOutPtrs &o, 
     };
     if (nc == N) {
         RETIF(copy_out(X.host, d, (size_t)nc * row));
-        if (h->host_prof)
+        if (h->knobs.host_prof)
             fprintf(stderr, "[lpc host]   export copy %.1f us (host %p, %zu B)\n", host_us() - hm, (void *)X.host,
                     (size_t)nc * row);
     } else {                                                    // chunk: each section at its rays' offset
@@ -2510,15 +2517,15 @@ static int enqueue_fused_chunk(lpc_handle *h, const IterPlan &I, const RaysIn &i
     const int64_t nt = (ng_rays + LPC_ST_TILE - 1) / LPC_ST_TILE;
     const int64_t nt_max = (nc + LPC_ST_TILE - 1) / LPC_ST_TILE;     // tiles the launch may touch
     StageArgs G;
-    G.S = shade_args(h, in, nullptr, nc, h->max_ray_len, h->ior_env, false);
+    G.S = shade_args(h, in, nullptr, nc, h->emitted.max_ray_len, h->emitted.ior_env, false);
     G.nd = ds ? ds->nd : nullptr;
     G.stR = (float *)h->w_shf.p; G.stT = (float *)h->w_shi.p;   // the 20 shade-output arrays hold the staging rows
     G.stM = (float *)h->w_soa.p; G.cst = (int64_t)Cs;
     G.tpow = (double *)h->w_fc.p; G.tcnt = (uint32_t *)(G.tpow + ntc); G.tdm = G.tcnt + ntc;
     G.skey = (unsigned long long *)h->w_key.p; G.scnt = (int32_t *)h->w_sc.p;
     // measured power per measure mesh summed on the way (no k_mesh_sum at the trace end)
-    G.nmp = h->meas_meshes.size() <= (size_t)LPC_MP_MAX ? (int)h->meas_meshes.size() : 0;
-    for (int m = 0; m < LPC_MP_MAX; ++m) G.mpm[m] = m < G.nmp ? h->meas_meshes[(size_t)m] : -1;
+    G.nmp = h->scene.meas_meshes.size() <= (size_t)LPC_MP_MAX ? (int)h->scene.meas_meshes.size() : 0;
+    for (int m = 0; m < LPC_MP_MAX; ++m) G.mpm[m] = m < G.nmp ? h->scene.meas_meshes[(size_t)m] : -1;
     G.tmp = (double *)(G.tdm + ntc);            // 16 ntc bytes in: 8-aligned
     const int64_t ng = (nt_max + LPC_ST_GROUP - 1) / LPC_ST_GROUP;
     unsigned long long *gs = (unsigned long long *)h->w_gsum.p;
@@ -2528,7 +2535,7 @@ static int enqueue_fused_chunk(lpc_handle *h, const IterPlan &I, const RaysIn &i
     G.cut = h->min_power; G.tcc = (uint32_t *)I.CS.cc; G.tcp = (double *)I.CS.cp;
     with_bool(I.cut, [&](auto ct) {     // (this nesting keeps the instantiations in their order in the code object)
         with_bool(ds != nullptr, [&](auto dsz) {
-            with_ku(h->K, [&](auto ku) {
+            with_ku(h->scene.K, [&](auto ku) {
                 hipLaunchKernelGGL((k_shade_stage<decltype(ku)::value, decltype(dsz)::value, decltype(ct)::value>),
                                    dim3((unsigned)nt), dim3(LPC_ST_TILE), 0, h->stream, G);
             });
@@ -2546,7 +2553,7 @@ static int enqueue_fused_chunk(lpc_handle *h, const IterPlan &I, const RaysIn &i
     M.gsum_next = gs + (size_t)(1 - h->gpar) * (size_t)h->gcap;
     M.gdirty_next = h->gdirty[1 - h->gpar];
     M.ctl = (IterCtl *)h->d_ctl.p; M.par = h->ctl_par;
-    M.thr = h->ds_thr; M.nmax = ds_cap(h); M.dcap2 = h->dcap * h->dcap * (1.0 - 1e-6);
+    M.thr = h->ds_thr; M.nmax = ds_cap(h); M.dcap2 = h->scene.dcap * h->scene.dcap * (1.0 - 1e-6);
     M.tbox = G.tbox; M.pbox = G.tbox ? (uint32_t *)h->d_pbox.p : nullptr;
     M.popT = nullptr; M.capT = 0; M.cbase_in = nullptr; M.cbase_out = nullptr;
     M.first = 1; M.last = 1;
@@ -2567,7 +2574,7 @@ static int enqueue_fused_chunk(lpc_handle *h, const IterPlan &I, const RaysIn &i
     });
     if (I.cut) cull_sum(h, I, base, nt_max, LPC_ST_TILE, ds ? ds->nd : nullptr);
     h->slots_clean = true;              // k_shade_stage restored what it read
-    h->slots_mrl = h->max_ray_len;
+    h->slots_mrl = h->emitted.max_ray_len;
     h->misc_clean = true;               // k_stage_move reset the next launch's words
     HIPCHK(h, hipGetLastError());
     return 0;
@@ -2613,15 +2620,15 @@ static int enqueue_plain_chunk(lpc_handle *h, const IterPlan &I, const IterOut &
     A.host_acc = I.host_acc;
     A.seq = I.seq;
     A.cut = h->min_power; A.blk_cc = (uint32_t *)I.CS.cc; A.blk_cp = (double *)I.CS.cp;
-    RETIF(run_shade(h, in, nullptr, nc, h->max_ray_len, h->ior_env, false));
+    RETIF(run_shade(h, in, nullptr, nc, h->emitted.max_ray_len, h->emitted.ior_env, false));
     with_bool(I.cut, [&](auto ct) {
         hipLaunchKernelGGL(k_count<decltype(ct)::value>, dim3((unsigned)A.nb), dim3(256), 0, h->stream, A);
     });
     if (I.cut) cull_sum(h, I, base, A.nb, 1024, nullptr);
     if (O.X) {
-        const double hx = h->host_prof ? host_us() : 0.0;
+        const double hx = h->knobs.host_prof ? host_us() : 0.0;
         RETIF(export_chunk(h, in, o, nc, base, I.N, *O.X));
-        if (h->host_prof) fprintf(stderr, "[lpc host]   export chunk %.1f us\n", host_us() - hx);
+        if (h->knobs.host_prof) fprintf(stderr, "[lpc host]   export chunk %.1f us\n", host_us() - hx);
     }
     if (O.per_ray()) RETIF(copy_per_ray(h, O, in, o, base, nc));
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, h->stream, A);
@@ -2648,14 +2655,14 @@ static int iter_enqueue(lpc_handle *h, const IterOut &O, const DevSize *ds, Pend
     const int64_t C = I.C = std::min(N, chunk_rays(h));
     if (ds && C < N) return set_err(h, LPC_E_STATE, "internal: device-sized iteration over one chunk only");
     I.ds = ds;
-    const double hp0 = h->host_prof ? host_us() : 0.0;
+    const double hp0 = h->knobs.host_prof ? host_us() : 0.0;
     RETIF(ensure_ws(h, C));
     RETIF(pop_reserve(h, h->B, 2 * N));
     if (!ds) RETIF(pop_reserve(h, h->T, N));
     // measured rows: the iterations still in flight may append up to their populations
     RETIF(ensure_measured(h, h->m_total + h->m_inflight + N));
     RETIF(cull_setup(h, &I));
-    if (h->host_prof)
+    if (h->knobs.host_prof)
         fprintf(stderr, "[lpc host]   buffers %.1f us (m_total %lld inflight %lld m_cap %lld)\n", host_us() - hp0,
                 (long long)h->m_total, (long long)h->m_inflight, (long long)h->m_cap);
     h->m_inflight += N;
@@ -2684,12 +2691,12 @@ static int iter_enqueue(lpc_handle *h, const IterOut &O, const DevSize *ds, Pend
     P->fused = traced;
     P->thr = h->ds_thr;
     // fused: it sums the measured power per measure mesh when they fit (StageArgs::nmp)
-    P->mp_fused = traced && h->meas_meshes.size() <= (size_t)LPC_MP_MAX;
+    P->mp_fused = traced && h->scene.meas_meshes.size() <= (size_t)LPC_MP_MAX;
     I.host_acc = early ? h->acc_map_dev + P->seq % kAccRing : nullptr;
     // fused: the children's origin box when they may be re-sorted (population >= LPC_RESORT_MIN)
-    I.want_box = traced && !ds && 2 * N >= h->resort_min;
+    I.want_box = traced && !ds && 2 * N >= h->knobs.resort_min;
     IsectIn ii;
-    ii.max_ray_len = h->max_ray_len; ii.dmax2 = h->pop.dmax2; ii.ds = ds;
+    ii.max_ray_len = h->emitted.max_ray_len; ii.dmax2 = h->pop.dmax2; ii.ds = ds;
     ii.trace = true; ii.traced = traced;
     const bool timed = h->prof.on && !h->prof.light;
     for (int64_t base = 0; base < N; base += C) {
@@ -2732,7 +2739,7 @@ static int iter_collect(lpc_handle *h, const Pending &P, float *out_next_pow, lp
     ++h->it_done;                       // the ledger's slot count (an empty iteration's slot stays zero)
     if (P.empty) { if (st) *st = S; return 0; }
     DevAcc acc;
-    const double t_wait = h->host_prof ? host_us() : 0.0;
+    const double t_wait = h->knobs.host_prof ? host_us() : 0.0;
     if (P.early) {
         RETIF(wait_mapped_acc(h, P.seq, &acc));
     } else {
@@ -2742,7 +2749,7 @@ static int iter_collect(lpc_handle *h, const Pending &P, float *out_next_pow, lp
     }
     h->m_inflight -= P.n_bound;
     if (acc.qerr) return q_failed(h);
-    if (h->host_prof) {
+    if (h->knobs.host_prof) {
         const double t_got = host_us();
         fprintf(stderr, "[lpc host] n %lld%s  since last %.1f us  wait %.1f us\n", (long long)P.n_in,
                 P.ds ? " (device-sized)" : "", t_wait - h->host_last, t_got - t_wait);
@@ -2801,13 +2808,13 @@ static void iter_discard(lpc_handle *h, const Pending &P)
 int lpc_trace_iterate(lpc_handle *h, float *out_origin4, float *out_dest4, float *out_pow,
                       int32_t *out_meas, float *out_next_pow, lpc_iter_stats *st)
 {
-    const double t_enter = h && h->host_prof ? host_us() : 0.0;
+    const double t_enter = h && h->knobs.host_prof ? host_us() : 0.0;
     if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
-    if (!h->traced_ready) return set_err(h, LPC_E_STATE, "trace_iterate before trace_set_rays");
+    RETIF(need_rays(h, "trace_iterate"));
     HIPCHK(h, hipSetDevice(h->device));
     Pending P;
     RETIF(iter_enqueue(h, IterOut{out_origin4, out_dest4, out_pow, out_meas, out_next_pow}, nullptr, &P));
-    if (h->host_prof && !P.empty)
+    if (h->knobs.host_prof && !P.empty)
         fprintf(stderr, "[lpc host] n %lld  launch %.1f us\n", (long long)P.n_in, host_us() - t_enter);
     return iter_collect(h, P, out_next_pow, st);
 }
@@ -2816,15 +2823,15 @@ int lpc_trace_iterate_export(lpc_handle *h, void *host, int32_t flags, lpc_iter_
 {
     if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
     if (!host) return set_err(h, LPC_E_ARG, "trace_iterate_export: null host block");
-    if (!h->traced_ready) return set_err(h, LPC_E_STATE, "trace_iterate_export before trace_set_rays");
+    RETIF(need_rays(h, "trace_iterate_export"));
     HIPCHK(h, hipSetDevice(h->device));
-    const double t_enter = h->host_prof ? host_us() : 0.0;
+    const double t_enter = h->knobs.host_prof ? host_us() : 0.0;
     const ExportSpec X{(char *)host, (flags & 1) ? 1 : 0};
     IterOut O;
     O.X = &X;
     Pending P;
     RETIF(iter_enqueue(h, O, nullptr, &P));
-    if (h->host_prof && !P.empty)
+    if (h->knobs.host_prof && !P.empty)
         fprintf(stderr, "[lpc host] n %lld  export launch %.1f us\n", (long long)P.n_in, host_us() - t_enter);
     return iter_collect(h, P, nullptr, st);
 }
@@ -2873,8 +2880,8 @@ int lpc_host_seq_sum_f32(const float *x, int64_t n, float *out)
 // and the host drops the iteration when the ranks' sums end the trace.
 static bool ds_ok(const lpc_handle *h, int64_t bound)
 {
-    return h->spec && h->acc_map_dev && (!h->prof.on || h->prof.light) && bound > 0 && bound <= chunk_rays(h) &&
-           bound < h->resort_min && (bound + 63) / 64 <= (int64_t)LPC_Q_MAX_PACKETS;
+    return h->knobs.spec && h->acc_map_dev && (!h->prof.on || h->prof.light) && bound > 0 && bound <= chunk_rays(h) &&
+           bound < h->knobs.resort_min && (bound + 63) / 64 <= (int64_t)LPC_Q_MAX_PACKETS;
 }
 
 // The trace loop (iterative_tracer.py:383-391).  With speculation (LPC_SPEC, and
@@ -2893,10 +2900,10 @@ static int trace_run(lpc_handle *h, int32_t max_iter, double power_threshold, lp
     if (!n_iter || (max_iter > 0 && !per_iter)) return set_err(h, LPC_E_ARG, "trace_run: null output");
     // mesh_power receives one double per mesh of the CURRENT scene: a buffer sized
     // for an earlier scene with fewer meshes is refused, not overrun
-    if (mesh_power && mesh_power_cap < h->K)
+    if (mesh_power && mesh_power_cap < h->scene.K)
         return set_err(h, LPC_E_ARG, "trace: mesh_power capacity below the scene's mesh count");
-    if (!h->traced_ready) return set_err(h, LPC_E_STATE, "trace_run before trace_set_rays");
-    if (h->host_prof)                           // the caller's time between traces
+    RETIF(need_rays(h, "trace_run"));
+    if (h->knobs.host_prof)                           // the caller's time between traces
         fprintf(stderr, "[lpc host] trace enter  since last %.1f us\n", host_us() - h->host_last);
     HIPCHK(h, hipSetDevice(h->device));
     *n_iter = 0;
@@ -2918,7 +2925,8 @@ static int trace_run(lpc_handle *h, int32_t max_iter, double power_threshold, lp
     // other ranks' power left after the last exchanged iteration j bounds theirs
     // at every later iteration (slack for the float32 children sums), and this
     // rank's power below threshold - that bound ends the global trace too.
-    const bool mono = h->xchg && h->mat_passive && h->pow_nonneg && h->ior_env > 0.0f && std::isfinite(h->ior_env);
+    const Emitted &E = h->emitted;
+    const bool mono = h->xchg && h->scene.mat_passive && E.pow_nonneg && E.ior_env > 0.0f && std::isfinite(E.ior_env);
     double others = INFINITY;           // upper bound of the other ranks' power left (last exchange)
     int32_t others_it = -1;
     auto local_thr = [&](int32_t it) {  // k_stage_move's stop threshold of iteration `it`
@@ -2989,7 +2997,7 @@ static int trace_run(lpc_handle *h, int32_t max_iter, double power_threshold, lp
                 if ((h->xchg || rebuilt) && (rc = restore_mrun(h))) {
                     // this iteration's exchange is done: the peers wait next in
                     // the trace-end sums (stop) or the next iteration's stats
-                    post_fail = stop ? ((measured_count || mesh_power) ? h->K + 2 : 0) : LPC_XCHG_STATS;
+                    post_fail = stop ? ((measured_count || mesh_power) ? h->scene.K + 2 : 0) : LPC_XCHG_STATS;
                     break;
                 }
             } else if (S.n_reflect + S.n_refract > nxt.n_bound || S.power_next < cur_thr) {
@@ -3028,23 +3036,23 @@ static int trace_run(lpc_handle *h, int32_t max_iter, double power_threshold, lp
     if (measured_count || mesh_power) {                     // the trace's aggregates, same call
         // [failure flag, per-mesh power (K), measured count]
         int64_t c = 0;
-        std::vector<double> mp((size_t)h->K + 2, 0.0);
-        if ((rc = lpc_trace_measured(h, &c, mp.data() + 1, h->K))) {
-            xchg_poison(h, h->K + 2);
+        std::vector<double> mp((size_t)h->scene.K + 2, 0.0);
+        if ((rc = lpc_trace_measured(h, &c, mp.data() + 1, h->scene.K))) {
+            xchg_poison(h, h->scene.K + 2);
             return rc;
         }
         if (h->xchg) {                                      // trace-end sums over the ranks
-            mp[(size_t)h->K + 1] = (double)c;
-            if (h->xchg(h->xchg_ctx, mp.data(), h->K + 2) != 0)
+            mp[(size_t)h->scene.K + 1] = (double)c;
+            if (h->xchg(h->xchg_ctx, mp.data(), h->scene.K + 2) != 0)
                 return set_err(h, LPC_E_STATE, "trace: all-reduce hook failed");
             if (mp[0] != 0.0) return set_err(h, LPC_E_STATE, "trace: a peer rank failed (failure flag in the trace-end sums)");
-            c = (int64_t)mp[(size_t)h->K + 1];
+            c = (int64_t)mp[(size_t)h->scene.K + 1];
         }
         if (measured_count) *measured_count = c;
-        if (mesh_power) memcpy(mesh_power, mp.data() + 1, (size_t)h->K * 8);
+        if (mesh_power) memcpy(mesh_power, mp.data() + 1, (size_t)h->scene.K * 8);
     }
     if (wait) RETIF(settle(h));                             // the trace's last kernels too
-    if (h->host_prof) {
+    if (h->knobs.host_prof) {
         const double t = host_us();
         fprintf(stderr, "[lpc host] trace leave  since last %.1f us\n", t - h->host_last);
         h->host_last = t;
@@ -3054,10 +3062,10 @@ static int trace_run(lpc_handle *h, int32_t max_iter, double power_threshold, lp
 
 static int mesh_power(lpc_handle *h, double *out)
 {
-    for (int32_t j = 0; j < h->K; ++j) out[j] = 0.0;
+    for (int32_t j = 0; j < h->scene.K; ++j) out[j] = 0.0;
     if (h->m_total == 0) return 0;
-    if (h->mp_valid && h->meas_meshes.size() <= (size_t)LPC_MP_MAX) {   // summed per tile by the traced iterations
-        for (size_t m = 0; m < h->meas_meshes.size(); ++m) out[h->meas_meshes[m]] = h->mp_last[m];
+    if (h->mp_valid && h->scene.meas_meshes.size() <= (size_t)LPC_MP_MAX) {  // summed per tile by the traced iterations
+        for (size_t m = 0; m < h->scene.meas_meshes.size(); ++m) out[h->scene.meas_meshes[m]] = h->mp_last[m];
         return 0;
     }
     const int64_t nb = (h->m_total + LPC_MSUM_TILE - 1) / LPC_MSUM_TILE;
@@ -3065,7 +3073,7 @@ static int mesh_power(lpc_handle *h, double *out)
     std::vector<double> part((size_t)nb);
     const size_t mc = (size_t)h->m_cap;
     const float *mf = (const float *)h->m_buf.p;
-    for (int32_t j : h->meas_meshes) {
+    for (int32_t j : h->scene.meas_meshes) {
         hipLaunchKernelGGL(k_mesh_sum, dim3((unsigned)nb), dim3(256), 0, h->stream, h->m_total,
                            mf + 3 * mc, (const int32_t *)(mf + 4 * mc), j, (double *)h->d_tmp.p);
         HIPCHK(h, hipGetLastError());
@@ -3081,7 +3089,7 @@ static int mesh_power(lpc_handle *h, double *out)
 int lpc_trace_measured(lpc_handle *h, int64_t *count, double *mesh_pow, int32_t mesh_pow_cap)
 {
     if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
-    if (mesh_pow && mesh_pow_cap < h->K)
+    if (mesh_pow && mesh_pow_cap < h->scene.K)
         return set_err(h, LPC_E_ARG, "trace_measured: mesh_power capacity below the scene's mesh count");
     HIPCHK(h, hipSetDevice(h->device));
     if (count) *count = h->m_total;
@@ -3662,7 +3670,7 @@ int lpc_trace_set_rays_dev(lpc_handle *h, lpc_rays *const *list, int32_t count, 
 {
     if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
     RETIF(settle(h));                   // a trace still running (lpc_trace_iterate / _run_async)
-    if (!h->M) return set_err(h, LPC_E_STATE, "no scene uploaded");
+    RETIF(need_scene(h));
     if (count < 0 || (count > 0 && !list)) return set_err(h, LPC_E_ARG, "set_rays_dev: missing source list");
     int64_t n = 0;
     for (int32_t k = 0; k < count; ++k) {
@@ -3674,8 +3682,6 @@ int lpc_trace_set_rays_dev(lpc_handle *h, lpc_rays *const *list, int32_t count, 
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     RETIF(pop_reserve(h, h->I, std::max<int64_t>(n, 1)));
-    RayScan S;
-    memset(&S, 0, sizeof(S));
     if (n > 0) {
         // the sources in list order, device to device; each after its producer's
         // last kernel (an event of the producing stream, no host wait)
@@ -3692,15 +3698,9 @@ int lpc_trace_set_rays_dev(lpc_handle *h, lpc_rays *const *list, int32_t count, 
             off += r->n;
         }
         HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)h->I.pmid(), -2, (size_t)n, h->stream));
-        RETIF(dalloc(h, h->d_scan, sizeof(RayScan)));
-        HIPCHK(h, hipMemsetAsync(h->d_scan.p, 0, sizeof(RayScan), h->stream));
-        hipLaunchKernelGGL(k_ray_scan, dim3((unsigned)std::min<int64_t>(grid1(n), 2048)), dim3(256), 0, h->stream,
-                           h->I.in(), n, h->box_lo[0], h->box_lo[1], h->box_lo[2], h->box_scale[0], h->box_scale[1],
-                           h->box_scale[2], (RayScan *)h->d_scan.p);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(&S, h->d_scan.p, sizeof(RayScan), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
     }
+    RayScan S;
+    RETIF(ray_scan(h, h->I.in(), n, h->d_scan, &S));
     return emitted_rays(h, n, S, max_ray_len, ior_env);
 }
 

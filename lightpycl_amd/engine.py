@@ -234,12 +234,11 @@ class Engine:
         last = getattr(self, "_scene_last", None)
         if last is not None and all(_same_digest(a, b) for a, b in zip(digest, last)):
             return
-        self._scene_last = None
+        # no scene while the call runs: one that raises leaves the object saying so
+        self.tri_count, self.mesh_count, self.mat_type, self._scene_last = 0, 0, None, None
         self._c(self.L.lpc_scene_upload(self.h, M, ptr(v0), ptr(v1), ptr(v2), ptr(mesh_id), K,
                                         ptr(mat_type), ptr(ior), ptr(refl), ptr(diss)))
-        self.tri_count, self.mesh_count = M, K
-        self.mat_type = mat_type
-        self._scene_last = digest
+        self.tri_count, self.mesh_count, self.mat_type, self._scene_last = M, K, mat_type, digest
 
     def upload_meshes(self, meshes):
         arrs = flatten_meshes(meshes)

@@ -357,3 +357,31 @@ def test_tracer_flatten_cache_follows_the_meshes():
     assert e is not d
     assert all(np.array_equal(p, q) for p, q in zip(e, flatten_meshes(sc.meshes[::-1])))
 
+
+
+def test_upload_arrays_that_raises_leaves_no_scene():
+    """Engine.upload_arrays clears tri_count, mesh_count, mat_type and the last
+    scene's digest together before the library call and sets them together after
+    it: a call that raises leaves the object saying "no scene" (measured() and
+    _bufs() size their buffers from the counts)."""
+    import types
+    from lightpycl_amd import _lib, scenes
+    from lightpycl_amd.engine import Engine, flatten_meshes
+    arrs = flatten_meshes(scenes.BUILDERS["nested_cubes"](n=10).meshes)
+    calls = []
+    eng = Engine.__new__(Engine)
+    eng.h = None
+    eng.L = types.SimpleNamespace(lpc_scene_upload=lambda *a: calls.append(a) or 0)
+    eng.upload_arrays(*arrs)
+    assert (eng.tri_count, eng.mesh_count) == (len(arrs[0]), len(arrs[4])) and eng.tri_count > 0
+    assert eng._scene_last is not None
+    assert np.array_equal(eng.mat_type, arrs[4])
+    eng.upload_arrays(*arrs)                                # the same scene: no second call
+    assert len(calls) == 1
+    eng.L.lpc_scene_upload = lambda *a: -1                  # LPC_E_ARG
+    v0 = arrs[0].copy()
+    v0[0, 0] += 1.0
+    with pytest.raises(_lib.LpcError):
+        eng.upload_arrays(v0, *arrs[1:])
+    assert eng.tri_count == 0 and eng.mesh_count == 0
+    assert eng.mat_type is None and eng._scene_last is None
