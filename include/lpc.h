@@ -291,6 +291,27 @@ int lpc_project_hist(lpc_handle *h, int mode, int64_t n, const float *pos4, cons
                      const double *yedges, int ny, double weight_div, double *H,
                      float *x, float *y, float *pwr_cor);
 
+/* ---- one-pass maps on the device (iterative_tracer.py:398-401, :564-657) ---- */
+/* Every point (n host points pos4 (n,4) + pwr[n], or with pos4 == NULL the
+ * trace's device-resident measured record) is read once, taken through each of
+ * the n_rot rotations rot4 (n_rot x 4x4 float32 rows, the reference's R_dev, rows
+ * 0-2 read; NULL = one identity) about pivot4 (NULL = origin) and binned into
+ * H[nx][ny] over the float64 edges as lpc_project_hist bins: numpy's rule, value
+ * == last edge in the last bin, outside or NaN dropped.  mode 0 = angular,
+ * 1 = stereographic (the projections of lpc_project_hist, bit for bit), 2 =
+ * planar: x, y are the rotated position's u, v (the position's own x, y when
+ * rot4 == NULL) and the weight is pwr.  Per binned point w = (double)pwr_cor /
+ * weight_div:  H += w, H2 += w * w, count += 1 (count and H2 may be NULL).  The
+ * counts are exact; the float64 sums are the reference's addends in atomic
+ * order, so their last bits vary from call to call.  Only H, count and H2 cross
+ * to the host.  n == 0 or an empty record gives zeros.  LPC_E_ARG (nothing
+ * launched): mode outside 0..2, n_rot < 1, nx or ny < 1, NULL edges or H, pos4
+ * without pwr, n < 0, nx * ny above 2^31 - 1. */
+int lpc_map_hist(lpc_handle *h, int mode, int64_t n, const float *pos4, const float *pwr,
+                 const float *rot4, int32_t n_rot, const float *pivot4,
+                 const double *xedges, int nx, const double *yedges, int ny, double weight_div,
+                 double *H, int64_t *count, double *H2);
+
 /* ---- beam analysis: elevation passes (iterative_tracer.py:420-501) -------- */
 /* The elevation of a point against `pole` (double[4]) is what numpy evaluates for
  * arccos(dot(pos / norm(pos, axis=1), pole)) on float32 (n,4) rows: float32 norm

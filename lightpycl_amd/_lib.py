@@ -92,6 +92,7 @@ _PROTOS = {
     "lpc_set_walk_grid": [_P, _I64],
     "lpc_project_hist": [_P, _INT, _I64, _P, _P, _P, _P, _P, _INT, _P, _INT, _F64, _P, _P, _P,
                          _P],
+    "lpc_map_hist": [_P, _INT, _I64, _P, _P, _P, _I32, _P, _P, _INT, _P, _INT, _F64, _P, _P, _P],
     "lpc_elev_scan": [_P, _I64, _P, _P, _P, _P],
     "lpc_elev_hist": [_P, _I64, _P, _P, _P, _P, _INT, _P, _P],
     "lpc_elev_digit_pass": [_P, _I64, _P, _P, _P, ctypes.c_uint64, _INT, _INT, _P, _P, _P],

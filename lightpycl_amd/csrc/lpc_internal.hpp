@@ -348,6 +348,27 @@ struct ProjArgs {
     double *H;
 };
 
+// One-pass maps (k_map_hist): the points as in ProjArgs, n_rot rotations applied
+// to every point, the histogram and its optional statistics.
+#define LPC_MAP_EDGES 2048            // edge doubles a block keeps in LDS (nx + ny + 2 at the most)
+#define LPC_MAP_ROTS 64               // rotations a block keeps in LDS at a time (rows 0-2, 12 floats each)
+#define LPC_MAP_HIST_BYTES 143360     // a block's histogram in LDS: 8 B per bin, 20 B with the statistics
+struct MapArgs {
+    int64_t n;
+    int mode;                         // 0 angular, 1 stereographic, 2 planar
+    int ident;                        // planar without a rotation: x, y are the position's own
+    const float4 *pos4;               // either pos4 or px/py/pz
+    const float *px, *py, *pz, *pwr;
+    const float *rot, *piv;           // device copies: n_rot x (4x4 rows), pivot 4
+    int n_rot;
+    const double *xe, *ye;
+    int nx, ny;
+    int slice_bins;                   // LDS path: bins per slice of the map (blockIdx.y)
+    double div;                       // w = (double)pc / div;  H += w, H2 += w * w, C += 1
+    double *H, *H2;                   // [nx][ny]; H2 and C only in the STATS instantiations
+    unsigned long long *C;
+};
+
 // Elevation analyses (k_elev_*): the points and the pole, then one pass's own
 // arguments.  Points: pos4 rows (host points, w as given) or the measured
 // record's px/py/pz (w = 0).

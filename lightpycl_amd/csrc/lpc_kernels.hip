@@ -30,6 +30,11 @@
 //                    (iterative_tracer.py:420-501): elevation range and totals,
 //                    np.histogram-compatible binning, one radix pass of the
 //                    half-power selection, power below an elevation.
+//   k_map_hist       one pass over the measured record for a whole 2-D map: all
+//                    source rotations of every ray projected (angular /
+//                    stereographic / planar) and binned on the device, with the
+//                    optional per-bin count and sum of squared weights
+//                    (iterative_tracer.py:398-401, :564-657).
 // Layout in HBM: SoA float/int32 arrays per ray; triangle records AoS (32 B
 // filter record, 48 B exact record, 36 B vertices), see DESIGN.md.
 #include <hip/hip_runtime.h>
@@ -2680,6 +2685,127 @@ __global__ __launch_bounds__(256) void k_elev_below(ElevBelowArgs A)
             atomicAdd(&A.out->power, ((s_p[0] + s_p[1]) + s_p[2]) + s_p[3]);
             atomicAdd(&A.out->count, cnt);
             atomicMax(&A.out->emax_bits, kmax);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// One-pass maps: every point is loaded once, projected
+// under each of the n_rot rotations (angular_project / stereograph_project /
+// planar_project, so the points are k_project_hist's bit for bit) and binned by
+// bin_index; w = (double)pc / div is added to H, and in the STATS instantiations
+// w * w to H2 and 1 to C.
+//   PATH 2  edges, rotations and the block's histogram in LDS (1024 threads, one
+//           block per CU); the bins the block touched are flushed once.  A map
+//           larger than a block's LDS goes in slices of slice_bins consecutive
+//           bins: the blocks of slice blockIdx.y sweep all points and keep the
+//           ones that fall into their bins.
+//   PATH 1  edges and rotations in LDS, global atomics per point (256 threads).
+//   PATH 0  as 1 with the edges read from global memory (nx + ny + 2 > LPC_MAP_EDGES).
+// A wave whose binned lanes all share one bin (rays near the pole, a focused
+// beam) reduces in registers and issues one atomic per array, as k_elev_digit.
+// The loops run on block-uniform bounds with the tail lanes masked by `i < n`:
+// the ballots and shuffles see whole waves.  Rotations beyond LPC_MAP_ROTS go in
+// further sweeps over the points.
+template <int PATH, bool STATS>
+__global__ __launch_bounds__(PATH == 2 ? 1024 : 256) void k_map_hist(MapArgs A)
+{
+    constexpr int BS = PATH == 2 ? 1024 : 256;
+    __shared__ double s_edge[PATH ? LPC_MAP_EDGES : 1];
+    __shared__ float s_rot[LPC_MAP_ROTS * 12];
+    __shared__ double s_raw[PATH == 2 ? LPC_MAP_HIST_BYTES / 8 : 1];
+    const int nx = A.nx, ny = A.ny;
+    const int b_lo = PATH == 2 ? (int)blockIdx.y * A.slice_bins : 0;      // this block's bins: [b_lo, b_lo + nb)
+    const int nb = PATH == 2 ? (nx * ny - b_lo < A.slice_bins ? nx * ny - b_lo : A.slice_bins) : nx * ny;
+    const double *xe = A.xe, *ye = A.ye;
+    if constexpr (PATH != 0) {
+        for (int t = threadIdx.x; t <= nx; t += BS) s_edge[t] = A.xe[t];
+        for (int t = threadIdx.x; t <= ny; t += BS) s_edge[nx + 1 + t] = A.ye[t];
+        xe = s_edge; ye = s_edge + nx + 1;
+    }
+    // LDS histogram: H[nb] | H2[nb] | C[nb] (uint32); zero bits are 0.0 and 0
+    double *s_H = s_raw, *s_H2 = s_raw + nb;
+    uint32_t *s_C = (uint32_t *)(s_raw + 2 * (size_t)nb);
+    if constexpr (PATH == 2) {
+        const int words = STATS ? 2 * nb + (nb + 1) / 2 : nb;
+        for (int t = threadIdx.x; t < words; t += BS) s_raw[t] = 0.0;
+    }
+    const int lane = threadIdx.x & 63;
+    const f3 piv = mk3(A.piv[0], A.piv[1], A.piv[2]);
+    const int64_t stride = (int64_t)gridDim.x * BS;
+    for (int r0 = 0; r0 < A.n_rot; r0 += LPC_MAP_ROTS) {
+        const int nr = A.n_rot - r0 < LPC_MAP_ROTS ? A.n_rot - r0 : LPC_MAP_ROTS;
+        __syncthreads();                                  // the sweep before is done with s_rot
+        for (int t = threadIdx.x; t < nr * 12; t += BS) s_rot[t] = A.rot[(int64_t)(r0 + t / 12) * 16 + t % 12];
+        __syncthreads();
+        for (int64_t base = (int64_t)blockIdx.x * BS; base < A.n; base += stride) {
+            const int64_t i = base + threadIdx.x;
+            const bool live = i < A.n;
+            f3 p = mk3(0.0f, 0.0f, 0.0f);
+            float pw = 0.0f;
+            if (live) {
+                if (A.pos4) { const float4 v = A.pos4[i]; p = mk3(v.x, v.y, v.z); }
+                else p = mk3(A.px[i], A.py[i], A.pz[i]);
+                pw = A.pwr[i];
+            }
+            for (int k = 0; k < nr; ++k) {
+                float x = p.x, y = p.y, pc = pw;
+                if (!A.ident) {
+                    const float *R = s_rot + k * 12;
+                    const f3 R0 = mk3(R[0], R[1], R[2]), R1 = mk3(R[4], R[5], R[6]), R2 = mk3(R[8], R[9], R[10]);
+                    if (A.mode == 0) angular_project(p, piv, R0, R1, R2, pw, x, y, pc);
+                    else if (A.mode == 1) stereograph_project(p, piv, R0, R1, R2, pw, x, y, pc);
+                    else planar_project(p, piv, R0, R1, pw, x, y, pc);
+                }
+                int b = -1;
+                if (live) {
+                    const int bx = bin_index((double)x, xe, nx), by = bin_index((double)y, ye, ny);
+                    if (bx >= 0 && by >= 0) b = bx * ny + by - b_lo;
+                    if (PATH == 2 && b >= nb) b = -1;             // (below b_lo: negative already)
+                }
+                const bool sel = b >= 0;
+                const uint64_t m = __ballot(sel);
+                if (m == 0) continue;
+                const double w = (double)pc / A.div;
+                const int b0 = __shfl(b, __ffsll((unsigned long long)m) - 1, 64);
+                if (!any_lane(sel && b != b0)) {
+                    const double s = wave_sum(sel ? w : 0.0);
+                    const double s2 = STATS ? wave_sum(sel ? w * w : 0.0) : 0.0;
+                    if (lane == 0) {
+                        if constexpr (PATH == 2) {
+                            atomicAdd(&s_H[b0], s);
+                            if (STATS) { atomicAdd(&s_H2[b0], s2); atomicAdd(&s_C[b0], (uint32_t)__popcll((unsigned long long)m)); }
+                        } else {
+                            atomicAdd(&A.H[b0], s);
+                            if (STATS) { atomicAdd(&A.H2[b0], s2); atomicAdd(&A.C[b0], (unsigned long long)__popcll((unsigned long long)m)); }
+                        }
+                    }
+                } else if (sel) {
+                    if constexpr (PATH == 2) {
+                        atomicAdd(&s_H[b], w);
+                        if (STATS) { atomicAdd(&s_H2[b], w * w); atomicAdd(&s_C[b], 1u); }
+                    } else {
+                        atomicAdd(&A.H[b], w);
+                        if (STATS) { atomicAdd(&A.H2[b], w * w); atomicAdd(&A.C[b], 1ull); }
+                    }
+                }
+            }
+        }
+    }
+    if constexpr (PATH == 2) {
+        __syncthreads();
+        for (int b = threadIdx.x; b < nb; b += BS) {
+            if (STATS) {
+                const uint32_t c = s_C[b];
+                if (c) {
+                    atomicAdd(&A.H[b_lo + b], s_H[b]);
+                    atomicAdd(&A.H2[b_lo + b], s_H2[b]);
+                    atomicAdd(&A.C[b_lo + b], (unsigned long long)c);
+                }
+            } else {
+                const double v = s_H[b];
+                if (v != 0.0) atomicAdd(&A.H[b_lo + b], v);      // (a NaN sum compares unequal too)
+            }
         }
     }
 }

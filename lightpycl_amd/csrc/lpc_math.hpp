@@ -341,6 +341,46 @@ LPC_HD void stereograph_project(f3 p, f3 piv, f3 R0, f3 R1, f3 R2, float pwr, fl
     x = xt; y = yt; pc = pwr / A;
 }
 
+// The planar view of the device maps (k_map_hist mode 2): the rotated position's
+// u, v as the two projections above form them, power unchanged.
+LPC_HD void planar_project(f3 p, f3 piv, f3 R0, f3 R1, float pwr, float &x, float &y, float &pc)
+{
+    LPC_EXACT
+    f3 vec = sub3(p, piv);
+    x = dot3(vec, R0) + piv.x;
+    y = dot3(vec, R1) + piv.y;
+    pc = pwr;
+}
+
+// ---------------------------------------------------------------------------
+// The bin of v among the monotone float64 edges e[0..nb]: numpy's histogramdd
+// rule, searchsorted(e, v, 'right') - 1 with a value equal to the last edge
+// counted in the last bin; -1 outside the edges and for NaN.  The answer is the
+// largest i with e[i] <= v < e[i + 1], whatever the guess below says: the guess
+// (the bin of uniformly spaced edges between e[0] and e[nb]) only chooses where
+// the comparison against the real edges starts.  Edges made by linspace put the
+// guess within one bin of the answer; after two steps each way without a hit
+// (arbitrary monotone edges) the bisection decides.
+LPC_HD int bin_index(double v, const double *e, int nb)
+{
+    const double lo = e[0], hi = e[nb];
+    if (!(v >= lo) || !(v <= hi)) return -1;              // outside (or NaN)
+    if (v == hi) return nb - 1;
+    // lo <= v < hi from here on, so hi > lo and e[nb] > v bounds every walk below
+    const double t = (v - lo) * ((double)nb / (hi - lo));
+    int g = t < (double)(nb - 1) ? (int)t : nb - 1;        // (a NaN or infinite t: the last bin)
+    if (g < 0) g = 0;
+    for (int k = 0; k < 2 && g > 0 && e[g] > v; ++k) --g;
+    for (int k = 0; k < 2 && g + 1 < nb && e[g + 1] <= v; ++k) ++g;
+    if (e[g] <= v && v < e[g + 1]) return g;
+    int a = 0, b = nb;                                      // e[a] <= v < e[b]
+    while (b - a > 1) {
+        const int mid = (a + b) >> 1;
+        if (e[mid] <= v) a = mid; else b = mid;
+    }
+    return a;
+}
+
 // ---------------------------------------------------------------------------
 // Elevation of a measured position against a pole, as the beam analyses
 // (iterative_tracer.py:420-501) evaluate it with numpy on float32 (n,4) rows and a

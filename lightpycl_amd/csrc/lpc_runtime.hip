@@ -193,6 +193,9 @@ struct Knobs {
                                                     //   2: also each launch's hand-over queue lengths (synchronising)
     int stage_mode = 0;                             // LPC_STAGE_MODE: 0 pageable DMA (round 6 A/B: 1.23-1.28 G fresh
                                                     //   rays), 1 pinned rows (0.83-0.93), 2 pinned SoA chunks (0.77-1)
+    int map_slices = 6;                             // LPC_MAP_SLICES: k_map_hist keeps the map in LDS while it fits this
+                                                    //   many slices (one sweep each); 0 = always global atomics
+    int map_per_cu = 8;                             // LPC_MAP_PER_CU: its blocks per CU on the global-atomic paths
 };
 
 // Every GPU resource of the handle is held by an owner of lpc_resource.hpp and
@@ -1412,6 +1415,8 @@ int lpc_open(int device, lpc_handle **out)
     k.spill_cap = std::max<int64_t>(env_int("LPC_SPILL_CAP", k.spill_cap), 64);
     k.host_prof = (int)env_int("LPC_HOSTPROF", 0);
     k.stage_mode = (int)std::min<int64_t>(2, std::max<int64_t>(0, env_int("LPC_STAGE_MODE", k.stage_mode)));
+    k.map_slices = (int)std::min<int64_t>(1024, std::max<int64_t>(0, env_int("LPC_MAP_SLICES", k.map_slices)));
+    k.map_per_cu = (int)std::min<int64_t>(64, std::max<int64_t>(1, env_int("LPC_MAP_PER_CU", k.map_per_cu)));
     if (h->acc_map.alloc(kAccRing * sizeof(DevAcc), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
         hipHostGetDevicePointer((void **)&h->acc_map_dev, h->acc_map, 0) != hipSuccess) {
         h->acc_map.reset();                          // counters then come by copy + stream sync
@@ -3177,6 +3182,99 @@ int lpc_project_hist(lpc_handle *h, int mode, int64_t n, const float *pos4, cons
         if (y) HIPCHK(h, hipMemcpy(y, A.y, (size_t)n * 4, hipMemcpyDeviceToHost));
         if (pwr_cor) HIPCHK(h, hipMemcpy(pwr_cor, A.pc, (size_t)n * 4, hipMemcpyDeviceToHost));
     }
+    return 0;
+}
+
+// One-pass map (k_map_hist): all rotations of every point binned on the device,
+// only the histogram (and its statistics) copied back.  With profiling on
+// (lpc_prof_enable) the launch's own start / stop timestamps go to kernel_ms.
+int lpc_map_hist(lpc_handle *h, int mode, int64_t n, const float *pos4, const float *pwr,
+                 const float *rot4, int32_t n_rot, const float *pivot4, const double *xedges, int nx,
+                 const double *yedges, int ny, double weight_div, double *H, int64_t *count, double *H2)
+{
+    if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
+    RETIF(settle(h));                   // a trace still running (lpc_trace_iterate / _run_async)
+    if (mode < 0 || mode > 2) return set_err(h, LPC_E_ARG, "map_hist: mode outside 0..2");
+    if (n_rot < 1) return set_err(h, LPC_E_ARG, "map_hist: n_rot < 1");
+    if (nx < 1 || ny < 1) return set_err(h, LPC_E_ARG, "map_hist: nx or ny < 1");
+    if (!xedges || !yedges || !H) return set_err(h, LPC_E_ARG, "map_hist: edges or H is NULL");
+    if (pos4 && !pwr) return set_err(h, LPC_E_ARG, "map_hist: pwr is NULL");
+    if (pos4 && n < 0) return set_err(h, LPC_E_ARG, "map_hist: negative n");
+    if ((int64_t)nx * ny > (int64_t)INT32_MAX) return set_err(h, LPC_E_ARG, "map_hist: nx * ny beyond 2^31 - 1 bins");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!pos4) n = h->m_total;
+    const bool stats = count || H2;
+    const size_t nb = (size_t)nx * ny, nr = rot4 ? (size_t)n_rot : 1;
+    // device scratch: [rot n_rot x 16 f | piv 4 f | xe | ye | H | H2 | C | (pos4, pwr)]
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t o_piv = nr * 64, o_xe = up(o_piv + 16), o_ye = o_xe + (size_t)(nx + 1) * 8;
+    const size_t o_H = up(o_ye + (size_t)(ny + 1) * 8);
+    const size_t o_in = up(o_H + nb * 8 * (stats ? 3 : 1));
+    RETIF(dalloc(h, h->d_tmp, o_in + (pos4 ? (size_t)n * 20 : 0) + 16));
+    char *d = (char *)h->d_tmp.p;
+    static const float eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0};
+    static const float zero4[4] = {0, 0, 0, 0};
+    HIPCHK(h, hipMemcpy(d, rot4 ? rot4 : eye, nr * 64, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d + o_piv, pivot4 ? pivot4 : zero4, 16, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d + o_xe, xedges, (size_t)(nx + 1) * 8, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d + o_ye, yedges, (size_t)(ny + 1) * 8, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemsetAsync(d + o_H, 0, nb * 8 * (stats ? 3 : 1), h->stream));
+    MapArgs A;
+    memset(&A, 0, sizeof(A));
+    A.n = n; A.mode = mode;
+    A.ident = mode == 2 && !rot4;
+    if (pos4) {
+        if (n > 0) {
+            HIPCHK(h, hipMemcpy(d + o_in, pos4, (size_t)n * 16, hipMemcpyHostToDevice));
+            HIPCHK(h, hipMemcpy(d + o_in + (size_t)n * 16, pwr, (size_t)n * 4, hipMemcpyHostToDevice));
+        }
+        A.pos4 = (const float4 *)(d + o_in);
+        A.pwr = (const float *)(d + o_in + (size_t)n * 16);
+    } else {
+        const size_t mc = (size_t)h->m_cap;
+        const float *mf = (const float *)h->m_buf.p;
+        A.px = mf; A.py = mf + mc; A.pz = mf + 2 * mc; A.pwr = mf + 3 * mc;
+    }
+    A.rot = (const float *)d; A.piv = (const float *)(d + o_piv); A.n_rot = (int)nr;
+    A.xe = (const double *)(d + o_xe); A.ye = (const double *)(d + o_ye);
+    A.nx = nx; A.ny = ny; A.div = weight_div;
+    A.H = (double *)(d + o_H);
+    if (stats) { A.H2 = A.H + nb; A.C = (unsigned long long *)(A.H2 + nb); }
+    if (n > 0) {
+        // the LDS histogram: a block holds cap_bins bins (20 B each with the statistics,
+        // 4 B of padding), a larger map goes in up to map_slices slices, each a sweep
+        // of its own over the points; the uint32 counts of a block cannot wrap
+        const bool edges_lds = (size_t)nx + ny + 2 <= LPC_MAP_EDGES;
+        const size_t cap_bins = (LPC_MAP_HIST_BYTES - 4) / (stats ? 20 : 8);
+        const size_t slices = (nb + cap_bins - 1) / cap_bins;
+        const bool hist_lds = h->knobs.map_slices > 0 && edges_lds && slices <= (size_t)h->knobs.map_slices &&
+                              (double)n * (double)nr < 4.0e9;
+        const int path = hist_lds ? 2 : edges_lds ? 1 : 0;
+        const int bs = path == 2 ? 1024 : 256;
+        A.slice_bins = (int)((nb + slices - 1) / slices);
+        const unsigned gy = path == 2 ? (unsigned)((nb + A.slice_bins - 1) / A.slice_bins) : 1u;
+        const int64_t cap = path == 2 ? std::max<int64_t>(1, std::max(h->cus, 1) / (int64_t)gy)
+                                      : (int64_t)std::max(h->cus, 1) * h->knobs.map_per_cu;
+        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + bs - 1) / bs, cap));
+        Event k0, k1;
+        const bool timed = h->prof.on && !h->prof.light;    // (light: k_rootwalk's events only)
+        if (timed) { k0 = ev_get(h); k1 = ev_get(h); }
+        auto launch = [&](auto pt, auto st) {
+            hipExtLaunchKernelGGL((k_map_hist<decltype(pt)::value, decltype(st)::value>), dim3(grid, gy), dim3(bs), 0,
+                                  h->stream, k0, k1, 0, A);
+        };
+        with_bool(stats, [&](auto st) {
+            if (path == 2) launch(std::integral_constant<int, 2>{}, st);
+            else if (path == 1) launch(std::integral_constant<int, 1>{}, st);
+            else launch(std::integral_constant<int, 0>{}, st);
+        });
+        HIPCHK(h, hipGetLastError());
+        if (timed) h->prof.ev_kern.emplace_back(std::move(k0), std::move(k1));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(H, A.H, nb * 8, hipMemcpyDeviceToHost));
+    if (H2) HIPCHK(h, hipMemcpy(H2, A.H2, nb * 8, hipMemcpyDeviceToHost));
+    if (count) HIPCHK(h, hipMemcpy(count, A.C, nb * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -580,6 +580,60 @@ class Engine:
                                         ptr(y), ptr(pc)))
         return (H, xe, ye) if not want_xy else (H, xe, ye, x, y, pc)
 
+    # -- one-pass maps -----------------------------------------------------------
+    @staticmethod
+    def _map_args(pos4, pwr, limits, points, mode, rots, pivot):
+        """The arguments of lpc_map_hist as arrays: (n, pos4, pwr, rots (k,4,4) or
+        None, pivot or None, xe, ye, divisor).  The edges are np.histogram2d's own;
+        the divisor is dx*dy for the projections (as project_hist) and 1 for the
+        planar view."""
+        if mode not in (0, 1, 2):
+            raise ValueError("mode is 0 (angular), 1 (stereographic) or 2 (planar)")
+        _, xe, ye = np.histogram2d(np.zeros(0), np.zeros(0), bins=points, range=limits)
+        xe = np.ascontiguousarray(xe, np.float64)
+        ye = np.ascontiguousarray(ye, np.float64)
+        if mode == 2:
+            div = 1.0
+        else:
+            px, py = (points, points) if np.ndim(points) == 0 else points
+            dx = np.float64(limits[0][1] - limits[0][0]) / np.float64(px)
+            dy = np.float64(limits[1][1] - limits[1][0]) / np.float64(py)
+            div = float(dx * dy)
+        if rots is not None:
+            rots = f32(rots)
+            if rots.ndim == 2:
+                rots = rots[None]
+            if rots.ndim != 3 or rots.shape[1:] != (4, 4) or rots.shape[0] < 1:
+                raise ValueError("rots is one (4,4) matrix or a (k,4,4) stack of them, k >= 1")
+            rots = np.ascontiguousarray(rots)
+        piv = None if pivot is None else f32(pivot).reshape(4)
+        if pos4 is None:
+            return 0, None, None, rots, piv, xe, ye, div
+        p4 = f32(pos4, (-1, 4))
+        pw = f32(pwr).reshape(-1)
+        if pw.size != p4.shape[0]:
+            raise ValueError("one power per point")
+        return p4.shape[0], p4, pw, rots, piv, xe, ye, div
+
+    def map_hist(self, pos4, pwr, limits, points, mode=0, rots=None, pivot=None, stats=False):
+        """One pass over the points on the GPU (lpc_map_hist): each is taken through
+        every rotation of ``rots`` ((k,4,4) rows as the reference's R_dev; None: one
+        identity), projected (mode 0 angular, 1 stereographic, 2 planar: the rotated
+        x, y) and binned as np.histogram2d(bins=points, range=limits) bins, weights
+        pwr_cor / (dx*dy) for the projections and pwr for the planar view.
+        pos4=None bins the device-resident measured record.  -> (H, xe, ye), with
+        ``stats`` (H, xe, ye, count, H2): the exact number of points per bin and
+        the per-bin sum of the squared weights."""
+        n, p4, pw, rots, piv, xe, ye, div = self._map_args(pos4, pwr, limits, points, mode, rots, pivot)
+        nx, ny = xe.size - 1, ye.size - 1
+        H = np.zeros((nx, ny), np.float64)
+        cnt = np.zeros((nx, ny), np.int64) if stats else None
+        H2 = np.zeros((nx, ny), np.float64) if stats else None
+        self._c(self.L.lpc_map_hist(self.h, int(mode), n, ptr(p4), ptr(pw), ptr(rots),
+                                    1 if rots is None else rots.shape[0], ptr(piv), ptr(xe), nx, ptr(ye), ny,
+                                    div, ptr(H), ptr(cnt), ptr(H2)))
+        return (H, xe, ye, cnt, H2) if stats else (H, xe, ye)
+
     # -- elevation passes (beam analysis) ---------------------------------------
     @staticmethod
     def _elev_points(pos4, pwr, pole):

@@ -395,7 +395,12 @@ class CL_Tracer:
                 pwr = np.concatenate((pwr.flatten(), pw[idx].flatten()), axis=0)
         return pos, pwr
 
-    def get_binned_data(self, limits=((-10, 10), (-10, 10)), points=500):
+    def get_binned_data(self, limits=((-10, 10), (-10, 10)), points=500, on_device=False):
+        """Planar map of the measured power (:398-401).  ``on_device=True`` bins on the
+        GPU (``lpc_map_hist``, planar view) instead of fetching the measured rays."""
+        if on_device:
+            self.hist_data = tuple(self._map(2, limits, points))
+            return self.hist_data
         (pos, pwr) = self.get_measured_rays()
         self.hist_data = np.histogram2d(x=pos[:, 0], y=pos[:, 1], bins=points, range=limits, weights=pwr)
         return self.hist_data
@@ -406,6 +411,42 @@ class CL_Tracer:
         pos, pwr = self.get_measured_rays()
         return self.engine.project_hist(pos, np.asarray(pwr).reshape(-1), limits, points, mode=mode, rot=rot,
                                         want_xy=want_xy)
+
+    def _map(self, mode, limits, points, rots=None, stats=False):
+        """Engine.map_hist of this trace's measured rays: the device-resident record
+        of an aggregate-mode trace, the measured rays as host points otherwise (the
+        split _project makes)."""
+        if self._aggregate:
+            return self.engine.map_hist(None, None, limits, points, mode=mode, rots=rots, stats=stats)
+        pos, pwr = self.get_measured_rays()
+        if pos is None:
+            pos, pwr = np.zeros((0, 4), np.float32), np.zeros(0, np.float32)
+        return self.engine.map_hist(pos, np.asarray(pwr).reshape(-1), limits, points, mode=mode, rots=rots,
+                                    stats=stats)
+
+    @staticmethod
+    def _source_rots(axis, sources):
+        """R(k 2 pi / sources) cast to float32, k = 0 .. sources - 1, as the loop of
+        replicate_lightsources_and_plot uploads them one by one (:598-601)."""
+        R = _rot(axis)
+        return np.stack([np.asarray(R(k * 2.0 * np.pi / sources), dtype=np.float32) for k in np.arange(sources)])
+
+    def binned_stats(self, kind, limits, points, axis="z", sources=1):
+        """A map on the GPU with its per-bin statistics -> (H, xe, ye, count, rel_err).
+        ``kind`` is "planar" (get_binned_data), "angular" or "stereographic"
+        (get_binned_data_angular / _stereographic); ``sources`` > 1 replicates the
+        source about ``axis`` as replicate_lightsources_and_plot does.  ``count`` is
+        the exact number of points in each bin and ``rel_err = sqrt(H2) / |H|`` with
+        H2 the bin's sum of squared weights (NaN for an empty bin, and for one whose
+        rays carry no power): it estimates the
+        standard error of a bin's power, relative to that power, under independent rays."""
+        mode = {"angular": 0, "stereographic": 1, "planar": 2}[kind]
+        rots = self._source_rots(axis, sources) if sources > 1 else None
+        H, xe, ye, count, H2 = self._map(mode, limits, points, rots=rots, stats=True)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rel_err = np.sqrt(H2) / np.abs(H)
+        rel_err[count == 0] = np.nan
+        return H, xe, ye, count, rel_err
 
     def get_binned_data_angular(self, limits=((-1, 1), (-1, 1)), points=500):
         """angular_project on the GPU + histogram2d binning on the GPU (:534-562)."""
@@ -418,12 +459,20 @@ class CL_Tracer:
         return self.hist_data
 
     def replicate_lightsources_and_plot(self, limits=((-10, 10), (-10, 10)), points=500, axis="z", sources=36,
-                                        use_3D=True, plot=True):
+                                        use_3D=True, plot=True, on_device=False):
         """Emulate ``sources`` rotated copies of the source by rotating the measured rays
         (:564-657): angular_project on the GPU per rotation (R(ang) rows as the
         reference's R_dev, :601), the projected points of all rotations
         concatenated and binned once with np.histogram2d, as the reference does
-        (:608-627)."""
+        (:608-627).  ``on_device=True`` makes one ``lpc_map_hist`` call over the same
+        rotations instead: the same points and addends, binned and summed on the
+        GPU (atomic order), and no point reaches the host."""
+        if on_device and sources >= 1:
+            H, xe, ye = self._map(0, limits, points, rots=self._source_rots(axis, sources))
+            self.hist_data = (H, xe, ye)
+            if plot:
+                self._plot(H, xe * 180.0 / np.pi, ye * 180.0 / np.pi, use_3D, "replicated_sources")
+            return self.hist_data
         R = _rot(axis)
         xs, ys, ps = [], [], []
         for k in np.arange(sources):
@@ -447,10 +496,12 @@ class CL_Tracer:
         return self.hist_data
 
     def plot_binned_data(self, limits=((-10, 10), (-10, 10)), points=500, use_3d=True, use_angular=False,
-                         hist_data=None):
+                         hist_data=None, on_device=False):
         if hist_data is None:
             if use_angular:
                 self.get_binned_data_angular(limits=limits, points=points)
+            elif on_device:
+                self.get_binned_data(limits=limits, points=points, on_device=True)
             else:
                 (pos, pwr) = self.get_measured_rays()
                 H, xc, yc = np.histogram2d(x=np.array(pos[:, 0].flatten()), y=np.array(pos[:, 1].flatten()),
