@@ -779,14 +779,7 @@ static __device__ __forceinline__ void sliver_group(const SliverArgs &A, int64_t
             const float e2x = bcast(S.e2x, k), e2y = bcast(S.e2y, k), e2z = bcast(S.e2z, k);
             const float sa = bcast(S.a, k), sbb = bcast(S.b, k);
             const f2 tx = ox - v0x, ty = oy - v0y, tz = oz - v0z;
-            const f2 cx = e2y * tz - e2z * ty;
-            const f2 cy = e2z * tx - e2x * tz;
-            const f2 cz = e2x * ty - e2y * tx;
-            const f2 x = dx * cx + dy * cy + dz * cz;
-            const f2 tm = {fmaxf(fmaxf(fabsf(tx.x), fabsf(ty.x)), fabsf(tz.x)),
-                           fmaxf(fmaxf(fabsf(tx.y), fabsf(ty.y)), fabsf(tz.y))};
-            const f2 rhs = dl * (sa + sbb * tm);
-            const f2 d = x * x - rhs * rhs;
+            const f2 d = sliver_line_test<f2>(e2x, e2y, e2z, sa, sbb, tx, ty, tz, dx, dy, dz, dl);
             ++n_tests;
             const bool r0 = d.x <= 0.0f, r1 = d.y <= 0.0f;
             if (!any_lane(r0 || r1)) continue;

@@ -547,6 +547,31 @@ struct SliverRec {
     int32_t ax1;            // 1: e2 holds E1 and e1 holds E2 (line filter about E1)
 };
 
+// The per-ray line filter of a sliver record (k_slivers' sliver_group, and the
+// host model walk of tests/csrc): with T = O - V0, tm = sliver_tmax(T), dl = |D|
+// and the record's filter edge e2 and constants (a, b) (sliver_params_axis), the
+// pair is a candidate when d = (D.(e2 x T))^2 - (dl (a + b tm))^2 <= 0.  F is
+// float, or lpc_f2 for two rays at once (the record's values are scalars either
+// way, each half one evaluation of the same formula).
+LPC_HD float sliver_tmax(float tx, float ty, float tz) { return fmaxf(fmaxf(fabsf(tx), fabsf(ty)), fabsf(tz)); }
+#if defined(__HIP__)
+LPC_HD lpc_f2 sliver_tmax(lpc_f2 tx, lpc_f2 ty, lpc_f2 tz)
+{
+    return lpc_f2{sliver_tmax(tx.x, ty.x, tz.x), sliver_tmax(tx.y, ty.y, tz.y)};
+}
+#endif
+template <class F>
+LPC_HD F sliver_line_test(float e2x, float e2y, float e2z, float a, float b, F tx, F ty, F tz, F dx, F dy, F dz, F dl)
+{
+    const F cx = e2y * tz - e2z * ty;
+    const F cy = e2z * tx - e2x * tz;
+    const F cz = e2x * ty - e2y * tx;
+    const F x = dx * cx + dy * cy + dz * cz;
+    const F tm = sliver_tmax(tx, ty, tz);
+    const F rhs = dl * (a + b * tm);
+    return x * x - rhs * rhs;
+}
+
 // Bound of one wave's packet of rays (k_packet): every origin lies within ro of
 // (ox,oy,oz) and every direction within angle th of the unit axis a.  all = 1
 // (incoherent packet, non-finite input) makes every packet test pass.

@@ -60,7 +60,8 @@ def _cmp_bounce(g, o, exact=True):
         if exact:
             np.testing.assert_array_equal(a, b, err_msg=k)
         else:
-            assert np.all((_ulps(a, b) <= 64) | (np.abs(np.float64(a) - b) <= 1e-6 * np.abs(b).max())), k
+            assert np.all((_ulps(a, b).reshape(np.shape(a)) <= 64) |
+                          (np.abs(np.float64(a) - b) <= 1e-6 * np.abs(b).max())), k
 
 
 @pytest.mark.parametrize("name,n", SCENES)
