@@ -848,28 +848,31 @@ __global__ __launch_bounds__(256) void k_gather_aos(const float4 *__restrict__ a
 }
 
 // k_gather_aos with the root tests of k_roots_s fused in (one task per packet:
-// at most 64 pieces, no run gate): 16 packets per 1024-thread block, each wave
-// gathers its packet's 64 rays and tests them against the pieces from the rows
-// it just read (the values k_roots_s would load from the gathered copy), then the
-// block reserves its items with one atomic, as k_roots_s does.  Lanes past n add
-// nothing (k_roots_s tests ray n - 1 there, which its own lane already covers).
+// at most 64 pieces, no run gate): one packet per wave, LPC_GR_T / 64 packets per
+// block; each wave gathers its packet's 64 rays and tests them against the pieces
+// from the rows it just read (the values k_roots_s would load from the gathered
+// copy), then the block reserves its items with one atomic, as k_roots_s does.
+// Lanes past n add nothing (k_roots_s tests ray n - 1 there, which its own lane
+// already covers).  A four-wave block is one wave per SIMD: it is placed as soon
+// as one walk wave per SIMD has left a CU, not four (DESIGN.md sections 5, 13).
+#define LPC_GR_T 256                       // threads per k_gather_roots block (queue_args sizes the shards by it)
 template <bool HALF>
-__global__ __launch_bounds__(1024) void k_gather_roots(const float4 *__restrict__ aos, int64_t n,
-                                                       const int32_t *__restrict__ perm, float *__restrict__ rs,
-                                                       int full, const Piece *__restrict__ pieces, int npieces,
-                                                       QueueArgs Q)
+__global__ __launch_bounds__(LPC_GR_T)
+void k_gather_roots(const float4 *__restrict__ aos, int64_t n, const int32_t *__restrict__ perm,
+                    float *__restrict__ rs, int full, const Piece *__restrict__ pieces, int npieces, QueueArgs Q)
 {
+    constexpr int nw = LPC_GR_T / 64;
     __shared__ float4 s_pc[64];
     __shared__ float s_pa[64];
-    __shared__ unsigned long long s_m[16];
-    __shared__ uint32_t s_off[17];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    __shared__ unsigned long long s_m[nw];
+    __shared__ uint32_t s_off[nw + 1];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if ((int)threadIdx.x < npieces) {
         const Piece &P = pieces[threadIdx.x];
         s_pc[threadIdx.x] = make_float4(P.cx, P.cy, P.cz, P.negB);
         s_pa[threadIdx.x] = P.negA;
     }
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t s = (int64_t)blockIdx.x * LPC_GR_T + threadIdx.x;
     const bool in = s < n;
     float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a;
     if (in) {
@@ -888,6 +891,7 @@ __global__ __launch_bounds__(1024) void k_gather_roots(const float4 *__restrict_
         float nx, ny, nz;
         unit_dir(D, nx, ny, nz);
         int p = 0;
+#pragma unroll 1        // two pieces in flight: 46 registers, allocated as 48 (unrolled: 64)
         for (; p + 1 < npieces; p += 2) {
             const float4 c0 = s_pc[p], c1 = s_pc[p + 1];
             const lpc_f2 cx = {c0.x, c1.x}, cy = {c0.y, c1.y}, cz = {c0.z, c1.z}, nb = {c0.w, c1.w};
@@ -1140,18 +1144,21 @@ __global__ __launch_bounds__(256) void k_ray_scan(RaysIn R, int64_t n, float bx0
 //   k_bprefix   per hi digit: exclusive prefix of the block counts, digit total
 //   k_bscatter  stable scatter by hi digit: (lo digit, ray) into bucket order;
 //               block 0 writes the bucket starts.  One level (lb = 0): perm
-//   k_bsort2    one block per hi bucket: stable order by lo digit in LDS, perm
-//               written in order
-// then k_gather_aos as after rocPRIM.  Replaces key + rocPRIM onesweep (4 fills,
+//   k_bsort2    one block per hi bucket and LPC_BS_RPB-entry chunk: stable order
+//               by lo digit in LDS, perm written in order
+// then the gather as after rocPRIM (k_gather_roots, or k_gather_aos where the
+// root tests are not fused in).  Replaces key + rocPRIM onesweep (4 fills,
 // 2 histogram and 2 look-back pass kernels for 1 M rays).  set_rays takes this
 // path only when a host estimate puts at most LPC_BS_MAXB rays into a hi bucket.
-#define LPC_BS_T 1024                      // threads per block
+#define LPC_BS_T 256                       // threads per block: four waves, one per SIMD
 #ifndef LPC_BS_RPB
-#define LPC_BS_RPB 4096                    // rays per k_bkey / k_bscatter block (-D: compile-time A/B)
+#define LPC_BS_RPB 1024                    // rays per k_bkey / k_bscatter block (-D: compile-time A/B)
 #endif
 #define LPC_BS_HB 8                        // hi digit bits (at most); lo digit <= 8 bits
 #define LPC_BS_ND (1 << LPC_BS_HB)
 #define LPC_BS_MAXB 16384                  // largest hi bucket the host estimate admits (k_bsort2 chunks)
+static_assert(LPC_BS_ND <= LPC_BS_T, "bs_round, bs_excl_scan: one thread per digit");
+static_assert(LPC_BS_RPB % LPC_BS_T == 0 && LPC_BS_MAXB % LPC_BS_RPB == 0, "whole rounds, whole chunks");
 
 // Rank of each lane's digit among the lower lanes with the same digit, and the
 // number of valid lanes with it (`valid` lanes only).
@@ -1180,8 +1187,7 @@ struct BSortLds {
 
 // One round of LPC_BS_T items (item j of the round on thread j): stable
 // positions from the running per-digit positions; `run` advances by the round's
-// counts.  The per-digit prefix over the 16 waves: 4 threads per digit (4 waves
-// each), combined with two shuffles.
+// counts.  The per-digit prefix over the waves: one thread per digit.
 static __device__ __forceinline__ uint32_t bs_round(BSortLds &S, uint32_t d, bool valid, int nbits, int nd)
 {
     const int t = threadIdx.x, w = t >> 6;
@@ -1190,40 +1196,23 @@ static __device__ __forceinline__ uint32_t bs_round(BSortLds &S, uint32_t d, boo
     wave_match(d, valid, nbits, rank, cnt, last);
     if (last) S.wc[w][d] = (uint16_t)cnt;
     __syncthreads();
-    {
-        const int e = t >> 2, g = t & 3;                // digit e, waves 4 g .. 4 g + 3
-        uint32_t c[4], p = 0;
-        if (e < nd) {
+    if (t < nd) {                                       // digit t (nd <= LPC_BS_ND == LPC_BS_T)
+        uint32_t o = S.run[t];
 #pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                c[v] = S.wc[4 * g + v][e];
-                S.wc[4 * g + v][e] = 0;
-                p += c[v];
-            }
+        for (int v = 0; v < LPC_BS_T / 64; ++v) {
+            const uint32_t c = S.wc[v][t];
+            S.wc[v][t] = 0;
+            S.off[v][t] = o;
+            o += c;
         }
-        uint32_t incl = p;                              // inclusive scan over the 4 threads of the digit
-        const uint32_t u1 = __shfl_up(incl, 1, 64);
-        if (g >= 1) incl += u1;
-        const uint32_t u2 = __shfl_up(incl, 2, 64);
-        if (g >= 2) incl += u2;
-        if (e < nd) {
-            uint32_t o = S.run[e] + incl - p;
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                S.off[4 * g + v][e] = o;
-                o += c[v];
-            }
-        }
-        // the digit's 4 threads are lanes of one wave: their reads of run[e] above
-        // are done before this write
-        if (e < nd && g == 3) S.run[e] += incl;
+        S.run[t] = o;
     }
     __syncthreads();
     return valid ? S.off[w][d] + (uint32_t)rank : 0u;
 }
 
-// dst[d] = base + sum of src[0 .. d) for d <= nd (nd < LPC_BS_T), block-wide; the
-// caller synchronises before reading dst.
+// dst[d] = base + sum of src[0 .. d) for d <= nd (1 <= nd <= LPC_BS_T), block-wide;
+// the caller synchronises before reading dst.
 static __device__ __forceinline__ void bs_excl_scan(const uint32_t *src, int nd, uint32_t base, uint32_t *dst,
                                                     uint32_t *ws)
 {
@@ -1238,7 +1227,8 @@ static __device__ __forceinline__ void bs_excl_scan(const uint32_t *src, int nd,
     __syncthreads();
     uint32_t e = base + incl - v;
     for (int k = 0; k < w; ++k) e += ws[k];
-    if (t <= nd) dst[t] = e;
+    if (t < nd) dst[t] = e;
+    if (t == nd - 1) dst[nd] = e + v;
 }
 
 // Keys of rays [b * RPB, (b + 1) * RPB) and their 32-byte rows (k_raykey), the
@@ -1315,7 +1305,10 @@ __global__ __launch_bounds__(LPC_BS_T) void k_bscatter(const uint32_t *__restric
     for (int i = t; i < (LPC_BS_T / 64) * LPC_BS_ND; i += LPC_BS_T) (&S.wc[0][0])[i] = 0;
     __syncthreads();
     if (t < nd) S.run[t] = st[t] + hist[(int64_t)t * nblk + blockIdx.x];
-    if (blockIdx.x == 0 && t <= nd) bst[t] = st[t];
+    if (blockIdx.x == 0) {
+        if (t < nd) bst[t] = st[t];
+        if (t == 0) bst[nd] = st[nd];
+    }
     const int64_t base = (int64_t)blockIdx.x * LPC_BS_RPB;
     constexpr int NR = LPC_BS_RPB / LPC_BS_T;
     uint32_t k[NR];
@@ -1367,8 +1360,8 @@ __global__ __launch_bounds__(LPC_BS_T) void k_bsort2(const uint8_t *__restrict__
     if (t < nl) { hl[t] = 0; hb4[t] = 0; }
     for (int i = t; i < (LPC_BS_T / 64) * LPC_BS_ND; i += LPC_BS_T) (&S.wc[0][0])[i] = 0;
     __syncthreads();
-    constexpr int IPT = LPC_BS_RPB / LPC_BS_T;
-    for (int64_t e0 = s0; e0 < s1; e0 += LPC_BS_RPB) {  // lo-digit counts: the bucket, and before c0
+    constexpr int IPT = 4;                              // loads in flight per thread (registers)
+    for (int64_t e0 = s0; e0 < s1; e0 += IPT * LPC_BS_T) {  // lo-digit counts: the bucket, and before c0
         uint32_t d[IPT];
 #pragma unroll
         for (int j = 0; j < IPT; ++j) {
@@ -1386,7 +1379,7 @@ __global__ __launch_bounds__(LPC_BS_T) void k_bsort2(const uint8_t *__restrict__
     bs_excl_scan(hl, nl, (uint32_t)s0, lst, ws);
     __syncthreads();
     if (t < nl) S.run[t] = lst[t] + hb4[t];
-    for (int64_t e0 = c0; e0 < c1; e0 += LPC_BS_RPB) {
+    for (int64_t e0 = c0; e0 < c1; e0 += IPT * LPC_BS_T) {
         uint32_t d[IPT];
 #pragma unroll
         for (int j = 0; j < IPT; ++j) {

@@ -185,6 +185,8 @@ struct Knobs {
                                                     //   (0: always; -1: never, k_slivers on the side stream)
     int64_t walk_grid = kWalkWaves;                 // LPC_WALK_GRID: k_rootwalk blocks
     bool spec = true;                               // LPC_SPEC: speculative iterations (trace_run)
+    bool bsort = true;                              // LPC_BSORT: 0 = the emitted rays sort by rocPRIM even where the
+                                                    //   counting sort fits (A/B and test hook; the order is the same)
     double dcap_init = 16.0;                        // LPC_DCAP_MILLI / 1000 (tests: a rebuild inside a trace)
     int spill_budget = 20;                          // LPC_BUDGET: node visits before a wave hands its work over (0 off)
     int64_t spill_large_per_tri = 16;               // LPC_LARGE_PER_TRI
@@ -912,8 +914,9 @@ static int queue_args(lpc_handle *h, int64_t n, const PieceTable *pt, const DevS
     }
     const int rs_S = b0.S, rs_pb = b0.pb;
     const int64_t rs_blocks = b0.blocks;
-    // k_gather_roots: 16 packets per block
-    rcap = std::max<int64_t>(rcap, ((((npk + 15) / 16) + LPC_Q_CSHARDS - 1) / LPC_Q_CSHARDS) * 16 *
+    // k_gather_roots: one packet per wave of its blocks
+    const int64_t gpb = LPC_GR_T / 64;
+    rcap = std::max<int64_t>(rcap, ((((npk + gpb - 1) / gpb) + LPC_Q_CSHARDS - 1) / LPC_Q_CSHARDS) * gpb *
                                        (int64_t)pt->npieces);
     if (rcap >= 0xffffffffLL) return set_err(h, LPC_E_ARG, "root items: too many per shard");
     RETIF(dalloc(h, h->w_qroots, (size_t)LPC_Q_CSHARDS * (size_t)rcap * 8));
@@ -1141,7 +1144,8 @@ static int run_intersect(lpc_handle *h, const IsectIn &a, IsectOut *out)
         int b0 = 0, b1 = 32;
         if (traced && h->pop.emitted) { b0 = h->emitted.init_key_lo; b1 = h->emitted.init_key_hi; }
         const int nbits = b1 - b0;
-        if (traced && h->pop.emitted && h->emitted.init_bsort && nbits >= 1 && nbits <= 16 && n >= LPC_MISC_WORDS) {
+        if (traced && h->pop.emitted && h->emitted.init_bsort && h->knobs.bsort && nbits >= 1 && nbits <= 16 &&
+            n >= LPC_MISC_WORDS) {
             // counting sort (MSD, two 8-bit digits, stable), then the gather
             const int hb = std::min(nbits, LPC_BS_HB), lb = nbits - hb;
             const int64_t nblk = (n + LPC_BS_RPB - 1) / LPC_BS_RPB;
@@ -1178,9 +1182,9 @@ static int run_intersect(lpc_handle *h, const IsectIn &a, IsectOut *out)
             QueueArgs Qf;
             QueueShape shf;
             RETIF(queue_args(h, n, pt, nullptr, &Qf, &shf));
-            const dim3 gg((unsigned)((n + 1023) / 1024));
+            const dim3 gg((unsigned)((n + LPC_GR_T - 1) / LPC_GR_T));
             with_bool(half, [&](auto hf) {
-                hipLaunchKernelGGL(k_gather_roots<decltype(hf)::value>, gg, dim3(1024), 0, h->stream,
+                hipLaunchKernelGGL(k_gather_roots<decltype(hf)::value>, gg, dim3(LPC_GR_T), 0, h->stream,
                                    (const float4 *)h->w_aos.p, n, perm, (float *)h->w_rs.p, traced ? 1 : 0,
                                    (const Piece *)pt->pieces.p, (int)pt->npieces, Qf);
             });
@@ -1409,6 +1413,7 @@ int lpc_open(int device, lpc_handle **out)
     k.sliver_merge = env_int("LPC_SLIVER_MERGE", k.sliver_merge);
     k.walk_grid = std::min<int64_t>(std::max<int64_t>(env_int("LPC_WALK_GRID", k.walk_grid), 64), 1 << 22);
     k.spec = env_int("LPC_SPEC", k.spec) != 0;
+    k.bsort = env_int("LPC_BSORT", k.bsort) != 0;
     k.dcap_init = (double)env_int("LPC_DCAP_MILLI", 16000) / 1000.0;
     k.spill_budget = (int)env_int("LPC_BUDGET", k.spill_budget);
     k.spill_large_per_tri = env_int("LPC_LARGE_PER_TRI", k.spill_large_per_tri);
