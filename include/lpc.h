@@ -425,6 +425,49 @@ int lpc_trace_set_min_power(lpc_handle *h, float min_power);
  * LPC_E_STATE. */
 int lpc_trace_culled(lpc_handle *h, int64_t *count, double *power, int32_t cap, int32_t *n_iter);
 
+/* ---- power budget --------------------------------------------------------- */
+/* Opt-in (default off: every result keeps its bits and the kernels launched are
+ * the ones launched without it).  With the ledger on, every traced ray of an
+ * iteration is booked, in float64 formed from the float32 values the shading
+ * read and wrote (p_in: the ray's power as read; p: after dissipation; kr / kt:
+ * the reflected / refracted child's power where the shading kept that child,
+ * else 0, before any cutoff):
+ *   dissipated  (double)p_in - (double)p         to mesh n1, when the dissipation
+ *                                                branch is taken (whatever the amount)
+ *   escaped     (double)p                        no hit within max_ray_len
+ *   terminated  (double)p                        hit, material type 2, to the hit mesh
+ *   measured    (double)p                        hit, material type 3, to the hit mesh
+ *   absorbed    ((double)p - (double)kr) - (double)kt   every other hit, to the hit
+ *               mesh: the Fresnel split's float32 residue on a refractive surface,
+ *               (1 - R) p on a mirror, the whole ray on a type-4 or unknown surface
+ *               and on the NaN-TIR path
+ *   kept        (double)kr + (double)kt          every ray (sum only)
+ * so that per iteration power_in = dissipated + escaped + terminated + measured +
+ * absorbed + kept, and kept_i - culled_i = power_in_{i+1} (culled: lpc_trace_culled),
+ * both up to float64 summation order.  NaN powers propagate into the sums.  The
+ * counts are exact; the float64 sums are added with atomics and may differ in
+ * their last bits from run to run. */
+typedef struct {
+    double power_in;         /* float64 sum of the iteration's float32 ray powers */
+    double dissipated, escaped, terminated, measured, absorbed, kept;
+    int64_t n_in, n_dissipated, n_escaped, n_terminated, n_measured, n_absorbed;
+} lpc_budget_iter;
+/* on != 0: the ledger is kept.  Holds until changed, from the next launched
+ * iteration.  Applies to every trace path (as lpc_trace_set_min_power), not to
+ * the per-kernel drop-ins or lpc_bounce_host. */
+int lpc_trace_set_budget(lpc_handle *h, int on);
+/* The ledger of the current trace.  *n_iter: the iterations since the ledger was
+ * cleared (0 when none of them ran with the ledger on; an iteration that ran
+ * with it off has a row of zeros); at most iter_cap rows are copied.
+ * mesh_power / mesh_count (K rows of 4, either may be NULL): dissipated,
+ * absorbed, terminated, measured per mesh, summed over the trace's iterations;
+ * mesh_cap < K with one of them given: LPC_E_ARG, nothing is written.  Cleared
+ * wherever the measured record is (set_rays, reset, rerun, run_staged,
+ * set_rays_dev).  Waits for the stream.  The ledger holds 16 384 iterations:
+ * with it on, an iteration past that fails with LPC_E_STATE. */
+int lpc_trace_budget(lpc_handle *h, lpc_budget_iter *per_iter, int32_t iter_cap, int32_t *n_iter,
+                     double *mesh_power, int64_t *mesh_count, int32_t mesh_cap);
+
 /* ---- diagnostics ---------------------------------------------------------- */
 /* The device's own conservative-filter code on n (ray, record) pairs, host
  * arrays: origin3/dir3 (n,3), rec5 (n,5) = centre xyz, negB, negA (filter_record /

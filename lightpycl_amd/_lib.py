@@ -28,6 +28,16 @@ class IterStats(ctypes.Structure):
                 ("power_next", ctypes.c_double), ("power_nonneg", ctypes.c_int64)]
 
 
+BUDGET_SUMS = ("power_in", "dissipated", "escaped", "terminated", "measured", "absorbed", "kept")
+BUDGET_COUNTS = ("n_in", "n_dissipated", "n_escaped", "n_terminated", "n_measured", "n_absorbed")
+BUDGET_MESH = ("dissipated", "absorbed", "terminated", "measured")       # the per-mesh table's columns
+
+
+class BudgetIter(ctypes.Structure):
+    """lpc_budget_iter: one iteration's row of the power budget."""
+    _fields_ = [(k, ctypes.c_double) for k in BUDGET_SUMS] + [(k, ctypes.c_int64) for k in BUDGET_COUNTS]
+
+
 class ElevSummary(ctypes.Structure):
     _fields_ = [("n_valid", ctypes.c_int64), ("n_invalid", ctypes.c_int64), ("n_negative", ctypes.c_int64),
                 ("e_min", ctypes.c_double), ("e_max", ctypes.c_double), ("total_power", ctypes.c_double)]
@@ -117,6 +127,8 @@ _PROTOS = {
     "lpc_trace_set_rays_dev": [_P, _P, _I32, _F32, _F32],
     "lpc_trace_set_min_power": [_P, _F32],
     "lpc_trace_culled": [_P, _P, _P, _I32, _P],
+    "lpc_trace_set_budget": [_P, _INT],
+    "lpc_trace_budget": [_P, _P, _I32, _P, _P, _P, _I32],
 }
 
 # lpc_allreduce_fn (include/lpc.h): int (*)(void *ctx, double *vals, int32_t n)

@@ -172,8 +172,37 @@ struct SlotInit {                     // per-mesh slot initial state of a launch
     uint32_t *tmask;                  // the written-slot masks to clear with the slots (or NULL)
 };
 
+// The power budget (lpc_trace_budget).  The shading
+// kernels' BUD instantiations write one fate record per ray of the chunk;
+// k_budget_sum books the records into the iteration's row and the per-mesh
+// staging table, k_budget_commit adds a collected iteration's staging table to
+// the trace's.
+struct BudgetRec {                    // [chunk rays] each (SoA)
+    int32_t *dn;                      // the mesh the ray dissipated in (the branch taken), else -1
+    int32_t *hit;                     // hit mesh, -1: none
+    float *pin, *p;                   // the power as read, after dissipation (ShadeOut::pow)
+    float *kr, *kt;                   // the kept children's powers as the shading wrote them (not kept: 0)
+};
+#define LPC_BUD_SUMS 7                    // power_in, dissipated, escaped, terminated, measured, absorbed, kept
+#define LPC_BUD_CNTS 6                    // n_in, n_dissipated, n_escaped, n_terminated, n_measured, n_absorbed
+#define LPC_BUD_LDS_MESHES 64             // meshes whose [4] table rows a block keeps in LDS (more: global atomics)
+struct BudgetRow {                    // lpc_budget_iter's layout
+    double s[LPC_BUD_SUMS];
+    unsigned long long c[LPC_BUD_CNTS];
+};
+struct BudgetSumArgs {
+    BudgetRec R;
+    int64_t n;                        // records of the launch (device-sized: its bound)
+    const long long *nd;              // device-sized launch: the records (NULL: n)
+    const int32_t *mat_type;
+    int32_t K;
+    BudgetRow *row;                   // the iteration's row (zeroed before its first chunk)
+    double *mp;                       // [K][4] staging table of the iteration: dissipated, absorbed,
+    unsigned long long *mc;           //   terminated, measured (zeroed before its first chunk)
+};
+
 struct CompactArgs {
-    int64_t n, nb;                    // rays in chunk, 1024-ray tiles
+    int64_t n, nb;                   // rays in chunk, 1024-ray tiles
     ShadeOutPtrs o;
     int32_t *blk_cnt;                 // [3][nb]
     long long *blk_off;               // [3][nb]
@@ -232,6 +261,8 @@ struct StageArgs {
     float cut;
     uint32_t *tcc;                    // [ntiles] culled children
     double *tcp;                      // [ntiles] their power
+    // power budget (the BUD instantiations only): the chunk's fate records
+    BudgetRec bud;
 };
 // The culled-power ledger (lpc_trace_culled): one slot per iteration of the
 // trace, written by k_cull_sum after the iteration's compaction.

@@ -1491,11 +1491,12 @@ static __device__ __forceinline__ ShadeOut shade_eval(const ShadeArgs &A, int64_
 }
 
 template <int KU = 0>
-static __device__ __forceinline__ ShadeOut shade_ray(const ShadeArgs &A, int64_t r)
+static __device__ __forceinline__ ShadeOut shade_ray(const ShadeArgs &A, int64_t r, PostOut *po_out = nullptr)
 {
     PostOut po;
     f3 dest;
     const ShadeOut s = shade_eval<KU>(A, r, po, dest);
+    if (po_out) *po_out = po;
     A.o.destx[r] = dest.x; A.o.desty[r] = dest.y; A.o.destz[r] = dest.z;
     A.o.imid[r] = po.hit_mesh;
     A.o.pw[r] = s.pow;
@@ -1517,6 +1518,34 @@ __global__ __launch_bounds__(256) void k_shade(ShadeArgs A)
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= A.n) return;
     (void)shade_ray<KU>(A, r);
+}
+
+// The power budget's fate record of ray r (BudgetRec; lpc.h has the ledger's
+// rule): pin is the power the shading read, po / s what it made of the ray.  The
+// dissipation test is shade()'s own (.cl:385-394).
+static __device__ __forceinline__ void budget_record(const BudgetRec &B, const ShadeArgs &A, int64_t r, float pin,
+                                                     const PostOut &po, const ShadeOut &s)
+{
+    const bool dis = po.n1 >= 0 && A.mat_type[po.n1] == 0 && A.diss[po.n1] > 0.000001f;
+    B.dn[r] = dis ? po.n1 : -1;
+    B.hit[r] = po.hit_mesh;
+    B.pin[r] = pin;
+    B.p[r] = s.pow;
+    B.kr[r] = s.r_meas == 0 ? s.r_pow : 0.0f;
+    B.kt[r] = s.t_meas == 0 ? s.t_pow : 0.0f;
+}
+
+// k_shade with the power budget on: the same shading and stores, and the ray's
+// fate record.
+template <int KU>
+__global__ __launch_bounds__(256) void k_shade_bud(ShadeArgs A, BudgetRec B)
+{
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= A.n) return;
+    const float pin = A.in.pw[r];
+    PostOut po;
+    const ShadeOut s = shade_ray<KU>(A, r, &po);
+    budget_record(B, A, r, pin, po, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -1755,7 +1784,9 @@ __global__ __launch_bounds__(256) void k_scatter(CompactArgs A)
 // with |power| < cut is dropped here, before anything counts it; the tile's culled
 // count and power (tcc / tcp) feed the ledger (k_cull_sum).  Its extra wave sums
 // and per-tile arrays exist only in that instantiation.
-template <int KU, bool DS, bool CUT = false>
+// BUD: the power budget's instantiation (lpc_trace_set_budget): every ray's fate
+// record (six stores, taken before the cutoff) for k_budget_sum.
+template <int KU, bool DS, bool CUT = false, bool BUD = false>
 __global__ __launch_bounds__(LPC_ST_TILE) void k_shade_stage(StageArgs A)
 {
     __shared__ double s_mp[LPC_MP_MAX][LPC_ST_TILE / 64];
@@ -1804,6 +1835,9 @@ __global__ __launch_bounds__(LPC_ST_TILE) void k_shade_stage(StageArgs A)
             if (A.skey[a] != k0) A.skey[a] = k0;
             if (A.scnt[a] != 0) A.scnt[a] = 0;
         }
+    }
+    if constexpr (BUD) {
+        if (in) budget_record(A.bud, S, r, S.in.pw[r], po, s);
     }
     bool fR = in && s.r_meas == 0, fT = in && s.t_meas == 0;
     const bool fM = in && s.meas == 1;
@@ -2265,6 +2299,100 @@ __global__ __launch_bounds__(256) void k_cull_sum(CullSumArgs A)
         if (!A.first) { v.count += A.slot->count; v.power = A.slot->power + v.power; }
         *A.slot = v;
     }
+}
+
+// The power budget of one chunk: its fate records booked into the iteration's
+// row and the iteration's per-mesh staging table (lpc.h has the terms; each is
+// formed in float64 by exactly those operations).  A thread sums its rays' terms,
+// waves and blocks reduce them, and a block adds its sums to the row with one
+// atomic per quantity; the per-mesh rows are privatised in LDS while the scene
+// has at most LPC_BUD_LDS_MESHES meshes, else every ray adds to the global table.
+// Counts are exact; the float64 sums depend on the atomics' order in their last
+// bits.  Device-sized launches read the record count on the device.
+__global__ __launch_bounds__(256) void k_budget_sum(BudgetSumArgs A)
+{
+    __shared__ double s_mp[LPC_BUD_LDS_MESHES * 4];
+    __shared__ unsigned int s_mc[LPC_BUD_LDS_MESHES * 4];
+    __shared__ double s_s[4][LPC_BUD_SUMS];
+    __shared__ unsigned long long s_c[4][LPC_BUD_CNTS];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const bool lds = A.K <= LPC_BUD_LDS_MESHES;
+    int64_t n = A.n;
+    if (A.nd) {
+        const long long nd = *A.nd;
+        n = nd > 0 ? min((int64_t)nd, A.n) : 0;
+    }
+    if (lds) {
+        for (int i = t; i < A.K * 4; i += 256) { s_mp[i] = 0.0; s_mc[i] = 0u; }
+        __syncthreads();
+    }
+    auto book = [&](int32_t mesh, int col, double v) {
+        if ((uint32_t)mesh >= (uint32_t)A.K) return;          // never expected: a mesh id outside the scene
+        const int i = mesh * 4 + col;
+        if (lds) { atomicAdd(&s_mp[i], v); atomicAdd(&s_mc[i], 1u); }
+        else { atomicAdd(&A.mp[i], v); atomicAdd(&A.mc[i], 1ull); }
+    };
+    double s[LPC_BUD_SUMS];
+    unsigned long long c[LPC_BUD_CNTS];
+#pragma unroll
+    for (int k = 0; k < LPC_BUD_SUMS; ++k) s[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < LPC_BUD_CNTS; ++k) c[k] = 0ull;
+    for (int64_t r = (int64_t)blockIdx.x * 256 + t; r < n; r += (int64_t)gridDim.x * 256) {
+        const int32_t dn = A.R.dn[r], hit = A.R.hit[r];
+        const double pin = (double)A.R.pin[r], p = (double)A.R.p[r];
+        const double kr = (double)A.R.kr[r], kt = (double)A.R.kt[r];
+        s[0] += pin; ++c[0];
+        if (dn >= 0) {
+            const double d = pin - p;
+            s[1] += d; ++c[1];
+            book(dn, 0, d);
+        }
+        if (hit < 0) {
+            s[2] += p; ++c[2];
+        } else {
+            const int32_t mt = hit < A.K ? A.mat_type[hit] : -1;
+            if (mt == 2) { s[3] += p; ++c[3]; book(hit, 2, p); }
+            else if (mt == 3) { s[4] += p; ++c[4]; book(hit, 3, p); }
+            else {
+                const double a = (p - kr) - kt;
+                s[5] += a; ++c[5];
+                book(hit, 1, a);
+            }
+        }
+        s[6] += kr + kt;
+    }
+#pragma unroll
+    for (int k = 0; k < LPC_BUD_SUMS; ++k) {
+        const double v = wave_sum(s[k]);
+        if (lane == 0) s_s[wv][k] = v;
+    }
+#pragma unroll
+    for (int k = 0; k < LPC_BUD_CNTS; ++k) {
+        unsigned long long v = c[k];
+        for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (lane == 0) s_c[wv][k] = v;
+    }
+    __syncthreads();
+    const bool any = s_c[0][0] + s_c[1][0] + s_c[2][0] + s_c[3][0] != 0ull;   // the block had rays
+    if (any && t < LPC_BUD_SUMS) atomicAdd(&A.row->s[t], ((s_s[0][t] + s_s[1][t]) + s_s[2][t]) + s_s[3][t]);
+    if (any && t >= 64 && t < 64 + LPC_BUD_CNTS) {
+        const int k = t - 64;
+        atomicAdd(&A.row->c[k], s_c[0][k] + s_c[1][k] + s_c[2][k] + s_c[3][k]);
+    }
+    if (lds && any)
+        for (int i = t; i < A.K * 4; i += 256)
+            if (s_mc[i]) { atomicAdd(&A.mp[i], s_mp[i]); atomicAdd(&A.mc[i], (unsigned long long)s_mc[i]); }
+}
+
+// A collected iteration's per-mesh staging table into the trace's (only
+// iterations the trace keeps are added: a speculative iteration that is dropped
+// leaves its staging table to be zeroed by the next user of it).
+__global__ __launch_bounds__(256) void k_budget_commit(double *mp_tot, unsigned long long *mc_tot, const double *mp,
+                                                       const unsigned long long *mc, int n)
+{
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
+        if (mc[i]) { mp_tot[i] += mp[i]; mc_tot[i] += mc[i]; }
 }
 
 // Population copy (trace reset: emitted rays -> current population), one launch.

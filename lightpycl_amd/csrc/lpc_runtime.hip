@@ -275,6 +275,15 @@ struct lpc_handle {
     DBuf w_cull;                                    // per-tile culled counts / powers of one launch
     bool cull_dirty = false;                        // some slot may be non-zero (cleared with the measured record)
     int64_t it_done = 0;                            // iterations collected since the trace's reset
+    // power budget (lpc_trace_set_budget) and its ledger (lpc_trace_budget)
+    bool budget = false;                            // off: the default instantiations of the shading kernels
+    DBuf d_bud;                                     // BudgetRow[kCullSlots]: one per iteration of the trace
+    DBuf d_bud_mesh;                                // per-mesh tables [3][K][4]: the trace's, two staging (iteration
+                                                    //   parity); the float64 sums, then the counts
+    DBuf w_bud;                                     // fate records of one chunk (BudgetRec: 6 arrays of ws_rays)
+    int32_t bud_K = 0;                              // the mesh count d_bud_mesh is laid out for
+    bool bud_dirty = false;                         // the ledger may be non-zero (cleared with the measured record)
+    bool bud_seen = false;                          // an iteration since the ledger was cleared ran with it on
     // trace
     Pop A, B, T, I;
     PopState pop;                                   // which of them is current, and as what
@@ -1986,6 +1995,12 @@ int lpc_trace_reset(lpc_handle *h)
         HIPCHK(h, hipMemsetAsync(h->d_cull.p, 0, h->d_cull.bytes, h->stream));
         h->cull_dirty = false;
     }
+    if (h->bud_dirty) {                             // the power budget likewise
+        if (h->d_bud.p) HIPCHK(h, hipMemsetAsync(h->d_bud.p, 0, h->d_bud.bytes, h->stream));
+        if (h->d_bud_mesh.p) HIPCHK(h, hipMemsetAsync(h->d_bud_mesh.p, 0, h->d_bud_mesh.bytes, h->stream));
+        h->bud_dirty = false;
+    }
+    h->bud_seen = false;
     return 0;
 }
 
@@ -2264,6 +2279,43 @@ int lpc_trace_culled(lpc_handle *h, int64_t *count, double *power, int32_t cap, 
     return 0;
 }
 
+int lpc_trace_set_budget(lpc_handle *h, int on)
+{
+    if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
+    h->budget = on != 0;                // from the next launched iteration
+    return 0;
+}
+
+static_assert(sizeof(lpc_budget_iter) == sizeof(BudgetRow), "lpc_budget_iter is BudgetRow's layout");
+
+int lpc_trace_budget(lpc_handle *h, lpc_budget_iter *per_iter, int32_t iter_cap, int32_t *n_iter,
+                     double *mesh_power, int64_t *mesh_count, int32_t mesh_cap)
+{
+    if (!h || !n_iter) return set_err(h, LPC_E_ARG, "null argument");
+    if (iter_cap < 0 || (iter_cap > 0 && !per_iter)) return set_err(h, LPC_E_ARG, "trace_budget: missing buffer");
+    if ((mesh_power || mesh_count) && mesh_cap < h->scene.K)
+        return set_err(h, LPC_E_ARG, "trace_budget: mesh capacity below the scene's mesh count");
+    RETIF(settle(h));
+    const int64_t n = h->bud_seen ? std::min<int64_t>(h->it_done, kCullSlots) : 0;
+    *n_iter = (int32_t)n;
+    const int64_t m = std::min<int64_t>(n, iter_cap);
+    const size_t kt = (size_t)h->scene.K * 4;
+    if (m > 0) memset(per_iter, 0, (size_t)m * sizeof(lpc_budget_iter));
+    if (mesh_power) memset(mesh_power, 0, kt * sizeof(double));
+    if (mesh_count) memset(mesh_count, 0, kt * sizeof(int64_t));
+    if (!h->bud_dirty) return 0;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (m > 0 && h->d_bud.p)
+        HIPCHK(h, hipMemcpyAsync(per_iter, h->d_bud.p, (size_t)m * sizeof(BudgetRow), hipMemcpyDeviceToHost, h->stream));
+    if (h->d_bud_mesh.p && h->bud_K == h->scene.K && kt > 0) {
+        const char *d = (const char *)h->d_bud_mesh.p;
+        if (mesh_power) HIPCHK(h, hipMemcpyAsync(mesh_power, d, kt * 8, hipMemcpyDeviceToHost, h->stream));
+        if (mesh_count) HIPCHK(h, hipMemcpyAsync(mesh_count, d + 3 * kt * 8, kt * 8, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
 int lpc_shm_comm_open(const char *name, int32_t rank, int32_t world, int32_t create, lpc_shm_comm **out)
 {
     if (!out) return set_err(nullptr, LPC_E_ARG, "shm comm: null output");
@@ -2374,6 +2426,8 @@ struct Pending {
     bool empty = false;         // nothing to do (n_in 0, host-sized)
     int64_t n_bound = 0;        // device-sized: population bound
     double thr = -INFINITY;     // fused: the stop threshold its k_stage_move applied (ds_thr)
+    bool bud = false;           // it ran with the power budget on: its per-mesh staging table ...
+    int bpar = 0;               // ... of this parity joins the trace's when it is collected
     PopState before;            // the population's role before its enqueue (undo of a discarded speculative iteration)
 };
 
@@ -2473,6 +2527,8 @@ struct IterPlan {
     bool want_box = false;                  // fused: the chunks write the children's origin box (d_pbox)
     bool cut = false;                       // power cutoff: the compaction's CUT instantiations ...
     CullSumArgs CS;                         // ... and the ledger's arguments (both cull_setup's)
+    bool bud = false;                       // power budget: the shading's BUD instantiations ...
+    BudgetSumArgs BS;                       // ... and the ledger's arguments (both budget_setup's)
 };
 
 // Power cutoff: this launch's per-tile culled sums and the iteration's ledger
@@ -2498,6 +2554,80 @@ static int cull_setup(lpc_handle *h, IterPlan *I)
     CS->cc = (const uint32_t *)(CS->cp + nt_ws);
     CS->slot = (CullSlot *)h->d_cull.p + slot;
     h->cull_dirty = true;
+    return 0;
+}
+
+// Power budget: the chunk's fate records, the iteration's row (the slot rule of
+// cull_setup) and its per-mesh staging table, both zeroed here, before the
+// iteration's first chunk: an iteration that is re-run starts from zero again,
+// and a dropped speculative iteration's sums never reach the trace's table
+// (iter_collect adds a kept iteration's).  Off: I->BS stays zero.
+static int budget_setup(lpc_handle *h, IterPlan *I, Pending *P)
+{
+    BudgetSumArgs *BS = &I->BS;
+    memset(BS, 0, sizeof(*BS));
+    I->bud = h->budget;
+    if (!I->bud) return 0;
+    const int64_t slot = h->it_done + (I->ds ? 1 : 0);
+    if (slot >= kCullSlots)
+        return set_err(h, LPC_E_STATE, "trace: the power budget holds " + std::to_string(kCullSlots) + " iterations");
+    if (!h->d_bud.p) {
+        RETIF(dalloc(h, h->d_bud, (size_t)kCullSlots * sizeof(BudgetRow)));
+        HIPCHK(h, hipMemsetAsync(h->d_bud.p, 0, h->d_bud.bytes, h->stream));
+    }
+    const int32_t K = h->scene.K;
+    const size_t kt = (size_t)K * 4;
+    if (!h->d_bud_mesh.p || h->bud_K != K) {
+        // (a scene with another mesh count comes with new rays: the ledger was cleared)
+        RETIF(dalloc(h, h->d_bud_mesh, 3 * kt * 16));
+        HIPCHK(h, hipMemsetAsync(h->d_bud_mesh.p, 0, h->d_bud_mesh.bytes, h->stream));
+        h->bud_K = K;
+    }
+    const size_t C = (size_t)h->ws_rays;
+    RETIF(dalloc(h, h->w_bud, 6 * C * 4));
+    float *f = (float *)h->w_bud.p;
+    BS->R.dn = (int32_t *)f; BS->R.hit = (int32_t *)(f + C);
+    BS->R.pin = f + 2 * C; BS->R.p = f + 3 * C; BS->R.kr = f + 4 * C; BS->R.kt = f + 5 * C;
+    BS->mat_type = (const int32_t *)h->scene.d_mat.p;
+    BS->K = K;
+    BS->row = (BudgetRow *)h->d_bud.p + slot;
+    const int par = (int)(slot & 1);
+    double *mp = (double *)h->d_bud_mesh.p;
+    unsigned long long *mc = (unsigned long long *)(mp + 3 * kt);
+    BS->mp = mp + (size_t)(1 + par) * kt;
+    BS->mc = mc + (size_t)(1 + par) * kt;
+    HIPCHK(h, hipMemsetAsync(BS->row, 0, sizeof(BudgetRow), h->stream));
+    HIPCHK(h, hipMemsetAsync(BS->mp, 0, kt * 8, h->stream));
+    HIPCHK(h, hipMemsetAsync(BS->mc, 0, kt * 8, h->stream));
+    h->bud_dirty = true;
+    P->bud = true;
+    P->bpar = par;
+    return 0;
+}
+
+// Power budget: the chunk's records into the iteration's row and staging table.
+static void budget_sum(lpc_handle *h, const IterPlan &I, int64_t nc, const long long *nd)
+{
+    BudgetSumArgs BS = I.BS;
+    BS.n = nc; BS.nd = nd;
+    const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>((nc + 255) / 256, 1024));
+    hipLaunchKernelGGL(k_budget_sum, dim3(nb), dim3(256), 0, h->stream, BS);
+}
+
+// Power budget: a collected iteration's staging table into the trace's.
+static int budget_commit(lpc_handle *h, const Pending &P)
+{
+    if (!P.bud || P.empty || !h->d_bud_mesh.p) return 0;
+    const size_t kt = (size_t)h->bud_K * 4;
+    if (kt == 0) return 0;
+    double *mp = (double *)h->d_bud_mesh.p;
+    unsigned long long *mc = (unsigned long long *)(mp + 3 * kt);
+    const unsigned nb = (unsigned)std::min<size_t>((kt + 255) / 256, 64);
+    hipLaunchKernelGGL(k_budget_commit, dim3(nb), dim3(256), 0, h->stream, mp, mc,
+                       (const double *)(mp + (size_t)(1 + P.bpar) * kt),
+                       (const unsigned long long *)(mc + (size_t)(1 + P.bpar) * kt), (int)kt);
+    HIPCHK(h, hipGetLastError());
+    h->inflight = true;
     return 0;
 }
 
@@ -2543,14 +2673,22 @@ static int enqueue_fused_chunk(lpc_handle *h, const IterPlan &I, const RaysIn &i
     G.tmask = tmask;
     G.tbox = I.want_box ? (uint32_t *)h->w_tbox.p : nullptr;
     G.cut = h->min_power; G.tcc = (uint32_t *)I.CS.cc; G.tcp = (double *)I.CS.cp;
-    with_bool(I.cut, [&](auto ct) {     // (this nesting keeps the instantiations in their order in the code object)
-        with_bool(ds != nullptr, [&](auto dsz) {
-            with_ku(h->scene.K, [&](auto ku) {
-                hipLaunchKernelGGL((k_shade_stage<decltype(ku)::value, decltype(dsz)::value, decltype(ct)::value>),
-                                   dim3((unsigned)nt), dim3(LPC_ST_TILE), 0, h->stream, G);
+    G.bud = I.BS.R;
+    // (this nesting keeps the instantiations in their order in the code object;
+    // the power budget's come after the others)
+    auto launch_stage = [&](auto bud) {
+        with_bool(I.cut, [&](auto ct) {
+            with_bool(ds != nullptr, [&](auto dsz) {
+                with_ku(h->scene.K, [&](auto ku) {
+                    hipLaunchKernelGGL((k_shade_stage<decltype(ku)::value, decltype(dsz)::value, decltype(ct)::value,
+                                                      decltype(bud)::value>),
+                                       dim3((unsigned)nt), dim3(LPC_ST_TILE), 0, h->stream, G);
+                });
             });
         });
-    });
+    };
+    if (!I.bud) launch_stage(std::false_type{});
+    else launch_stage(std::true_type{});
     MoveArgs M;
     M.ntiles = nt_max; M.ngroups = ng;
     M.stR = G.stR; M.stT = G.stT; M.stM = G.stM; M.cst = G.cst;
@@ -2583,6 +2721,7 @@ static int enqueue_fused_chunk(lpc_handle *h, const IterPlan &I, const RaysIn &i
         hipLaunchKernelGGL(k_stage_move<decltype(dsz)::value>, dim3((unsigned)nt), dim3(LPC_ST_TILE), 0, h->stream, M);
     });
     if (I.cut) cull_sum(h, I, base, nt_max, LPC_ST_TILE, ds ? ds->nd : nullptr);
+    if (I.bud) budget_sum(h, I, nc, ds ? ds->nd : nullptr);
     h->slots_clean = true;              // k_shade_stage restored what it read
     h->slots_mrl = h->emitted.max_ray_len;
     h->misc_clean = true;               // k_stage_move reset the next launch's words
@@ -2630,7 +2769,16 @@ static int enqueue_plain_chunk(lpc_handle *h, const IterPlan &I, const IterOut &
     A.host_acc = I.host_acc;
     A.seq = I.seq;
     A.cut = h->min_power; A.blk_cc = (uint32_t *)I.CS.cc; A.blk_cp = (double *)I.CS.cp;
-    RETIF(run_shade(h, in, nullptr, nc, h->emitted.max_ray_len, h->emitted.ior_env, false));
+    if (I.bud) {                        // k_shade with the fate records, and their sums
+        const ShadeArgs SA = shade_args(h, in, nullptr, nc, h->emitted.max_ray_len, h->emitted.ior_env, false);
+        with_ku(h->scene.K, [&](auto ku) {
+            hipLaunchKernelGGL(k_shade_bud<decltype(ku)::value>, dim3(grid1(nc)), dim3(256), 0, h->stream, SA, I.BS.R);
+        });
+        HIPCHK(h, hipGetLastError());
+        budget_sum(h, I, nc, nullptr);
+    } else {
+        RETIF(run_shade(h, in, nullptr, nc, h->emitted.max_ray_len, h->emitted.ior_env, false));
+    }
     with_bool(I.cut, [&](auto ct) {
         hipLaunchKernelGGL(k_count<decltype(ct)::value>, dim3((unsigned)A.nb), dim3(256), 0, h->stream, A);
     });
@@ -2656,6 +2804,7 @@ static int iter_enqueue(lpc_handle *h, const IterOut &O, const DevSize *ds, Pend
 {
     *P = Pending();
     P->before = h->pop;
+    if (h->budget) h->bud_seen = true;  // (an empty population too: its row is zeros)
     IterPlan I;
     const int64_t N = I.N = ds ? ds->bound : h->pop.n;
     P->n_in = ds ? -1 : N;
@@ -2672,6 +2821,7 @@ static int iter_enqueue(lpc_handle *h, const IterOut &O, const DevSize *ds, Pend
     // measured rows: the iterations still in flight may append up to their populations
     RETIF(ensure_measured(h, h->m_total + h->m_inflight + N));
     RETIF(cull_setup(h, &I));
+    RETIF(budget_setup(h, &I, P));
     if (h->knobs.host_prof)
         fprintf(stderr, "[lpc host]   buffers %.1f us (m_total %lld inflight %lld m_cap %lld)\n", host_us() - hp0,
                 (long long)h->m_total, (long long)h->m_inflight, (long long)h->m_cap);
@@ -2748,6 +2898,7 @@ static int iter_collect(lpc_handle *h, const Pending &P, float *out_next_pow, lp
     S.power_nonneg = 1;
     ++h->it_done;                       // the ledger's slot count (an empty iteration's slot stays zero)
     if (P.empty) { if (st) *st = S; return 0; }
+    RETIF(budget_commit(h, P));
     DevAcc acc;
     const double t_wait = h->knobs.host_prof ? host_us() : 0.0;
     if (P.early) {

@@ -245,6 +245,27 @@ class ShardedTrace:
             tot = self._sum(np.concatenate((np.asarray(cc, np.float64), np.asarray(cp, np.float64))))
             out["culled_counts"] = [int(v) for v in tot[:k]]
             out["culled_power"] = [float(v) for v in tot[k:2 * k]]
+        if getattr(self.engine, "budget_on", False):
+            # the power budget (Engine.set_budget, on every rank alike) summed over
+            # the ranks in the same way: `iters` rows of 13 and the (K, 4) tables,
+            # sizes that no rank's data changes (counts are exact in float64)
+            from . import _lib
+            from .iterative_tracer import budget_dict
+            b = self.engine.budget()
+            names = _lib.BUDGET_SUMS + _lib.BUDGET_COUNTS
+            rows = np.zeros((len(names), iters), np.float64)
+            for j, name in enumerate(names):
+                v = np.asarray(b[name], np.float64)[:iters]
+                rows[j, :len(v)] = v
+            kk = b["mesh_power"].size
+            tot = self._sum(np.concatenate((rows.ravel(), b["mesh_power"].ravel(),
+                                            b["mesh_count"].astype(np.float64).ravel())))
+            rows = tot[:rows.size].reshape(len(names), iters)
+            g = {name: (rows[j] if name in _lib.BUDGET_SUMS else np.rint(rows[j]).astype(np.int64))
+                 for j, name in enumerate(names)}
+            g["mesh_power"] = tot[rows.size:rows.size + kk].reshape(-1, 4)
+            g["mesh_count"] = np.rint(tot[rows.size + kk:]).astype(np.int64).reshape(-1, 4)
+            out["power_budget"] = budget_dict(g, out.get("culled_counts", ()), out.get("culled_power", ()))
         if hist is not None:
             limits, points = hist
             H, xe, ye = self.engine.project_hist(None, None, limits, points)[:3]

@@ -197,6 +197,7 @@ class Engine:
         self.tri_count = 0
         self.mesh_count = 0
         self.min_power = 0.0
+        self.budget_on = False
 
     # -- lifecycle -----------------------------------------------------------
     def close(self):
@@ -388,6 +389,35 @@ class Engine:
         if n.value:
             self._c(self.L.lpc_trace_culled(self.h, ptr(cnt), ptr(pw), n.value, ctypes.byref(n)))
         return cnt[: n.value], pw[: n.value]
+
+    def set_budget(self, on):
+        """lpc_trace_set_budget: keep the power budget (off by default); holds
+        until changed, from the next launched iteration."""
+        self._c(self.L.lpc_trace_set_budget(self.h, 1 if on else 0))
+        self.budget_on = bool(on)
+
+    def budget(self):
+        """lpc_trace_budget: the power budget of the current trace -> a dict of
+        per-iteration arrays (``power_in``, ``dissipated``, ``escaped``,
+        ``terminated``, ``measured``, ``absorbed``, ``kept`` float64; ``n_in``,
+        ``n_dissipated`` ... ``n_absorbed`` int64), ``mesh_power`` (float64 (K, 4))
+        and ``mesh_count`` (int64 (K, 4)), columns dissipated, absorbed, terminated,
+        measured (``_lib.BUDGET_MESH``).  No rows when no iteration since the rays
+        were set / reset ran with the ledger on."""
+        n = ctypes.c_int32(0)
+        self._c(self.L.lpc_trace_budget(self.h, None, 0, ctypes.byref(n), None, None, 0))
+        rows = (_lib.BudgetIter * max(n.value, 1))()
+        k = int(self.mesh_count)
+        mp, mc = np.zeros((k, 4), np.float64), np.zeros((k, 4), np.int64)
+        self._c(self.L.lpc_trace_budget(self.h, ctypes.cast(rows, ctypes.c_void_p), n.value, ctypes.byref(n),
+                                        ptr(mp), ptr(mc), k))
+        out = {}
+        for name in _lib.BUDGET_SUMS:
+            out[name] = np.array([getattr(rows[i], name) for i in range(n.value)], np.float64)
+        for name in _lib.BUDGET_COUNTS:
+            out[name] = np.array([getattr(rows[i], name) for i in range(n.value)], np.int64)
+        out["mesh_power"], out["mesh_count"] = mp, mc
+        return out
 
     def reset(self):
         self._c(self.L.lpc_trace_reset(self.h))

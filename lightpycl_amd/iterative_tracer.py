@@ -55,6 +55,50 @@ def f32_sorted_sum(a):
     return np.float32(out.value)
 
 
+def budget_dict(b, culled_counts=(), culled_power=()):
+    """The power budget as the tracer returns it, from ``Engine.budget()`` and the
+    culled-power ledger of the same trace (empty: no cutoff).
+
+    Per iteration (arrays over the trace's iterations): ``power_in`` and the six
+    float64 sums ``dissipated`` (Beer-Lambert loss inside a medium), ``escaped``
+    (no hit within max_ray_len), ``terminated`` (terminator surfaces),
+    ``measured`` (measure surfaces), ``absorbed`` (what every other hit did not
+    hand to its children: (1 - R) p on a mirror, the whole ray on a type-4 or
+    unknown surface and on the NaN-TIR path, the float32 residue of the Fresnel
+    split on a refractive surface) and ``kept`` (the children's power before
+    any cutoff), with the exact counts ``n_in``, ``n_dissipated``, ``n_escaped``,
+    ``n_terminated``, ``n_measured``, ``n_absorbed``; ``culled`` and ``n_culled``
+    from the cutoff's ledger (zeros without one).
+
+    ``mesh``: ``{category: float64[K]}`` and ``mesh_count``: ``{category:
+    int64[K]}`` for dissipated (the medium's mesh), absorbed, terminated and
+    measured (the hit mesh), summed over the trace.
+
+    ``left``: the last iteration's kept power minus its culled power, the power
+    of the population the stop rule left untraced.  ``closure``: the residue of
+    the whole-trace identity, ``power_in[0]`` minus every iteration's
+    dissipated, escaped, terminated, measured, absorbed and culled power minus
+    ``left``: float64 rounding of the sums when the ledger is whole."""
+    import math
+    from . import _lib
+    n = len(b["n_in"])
+    out = {k: np.asarray(b[k]) for k in _lib.BUDGET_SUMS + _lib.BUDGET_COUNTS}
+    cp = np.zeros(n, np.float64)
+    cc = np.zeros(n, np.int64)
+    m = min(n, len(culled_power))
+    cp[:m] = np.asarray(culled_power, np.float64)[:m]
+    cc[:m] = np.asarray(culled_counts, np.int64)[:m]
+    out["culled"], out["n_culled"] = cp, cc
+    out["mesh"] = {k: np.asarray(b["mesh_power"])[:, j].copy() for j, k in enumerate(_lib.BUDGET_MESH)}
+    out["mesh_count"] = {k: np.asarray(b["mesh_count"])[:, j].copy() for j, k in enumerate(_lib.BUDGET_MESH)}
+    left = float(out["kept"][-1] - cp[-1]) if n else 0.0
+    spent = [float(v) for k in ("dissipated", "escaped", "terminated", "measured", "absorbed", "culled")
+             for v in out[k]]
+    out["left"] = left
+    out["closure"] = math.fsum([float(out["power_in"][0])] + [-v for v in spent] + [-left]) if n else 0.0
+    return out
+
+
 # the tracer's helper thread (created with the module, started on first use)
 _SUM_POOL = ThreadPoolExecutor(max_workers=1, thread_name_prefix="lpc-sum")
 
@@ -146,7 +190,7 @@ class CL_Tracer:
 
     def iterative_tracer(self, light_source, meshes, trace_iterations=100, trace_until_dissipated=0.99,
                          max_ray_len=np.float32(1e3), ior_env=np.float32(1.0), keep_results=True,
-                         min_ray_power=0.0):
+                         min_ray_power=0.0, power_budget=False):
         """Trace until ``trace_iterations`` bounces, until less than
         (1 - trace_until_dissipated) of the input power is left, or until no ray is
         left (iterative_tracer.py:241-391).  Returns ``self.results``.
@@ -163,10 +207,17 @@ class CL_Tracer:
         :meth:`power_culled` the total: with non-negative powers and passive
         materials each measure mesh loses at most that much (DESIGN.md section
         11).  Culled power no longer counts as power left, so a trace may stop an
-        iteration earlier than without the cutoff."""
+        iteration earlier than without the cutoff.
+
+        ``power_budget=True`` (default off; set on every call) keeps the trace's
+        power budget on the device: where every ray's power went, per iteration
+        and per mesh.  :meth:`power_budget` returns it afterwards (DESIGN.md
+        section 14).  The trace's results keep their bits with it on or off."""
         max_ray_len = np.float32(max_ray_len)
         ior_env = np.float32(ior_env)
         self.engine.set_min_power(min_ray_power)
+        self.engine.set_budget(power_budget)
+        self._budget = None
         self.culled_counts, self.culled_power = [], []
         clk = time.perf_counter
         ph = {}                                 # host-side phases of this call (self.phase_s)
@@ -262,6 +313,7 @@ class CL_Tracer:
             ph["loop"] = clk() - t_ph
             t_ph = clk()
             self._read_culled()
+            self._read_budget()
         finally:
             self.engine.sync()                  # the exported results arrays are complete
         ph["sync"] = clk() - t_ph
@@ -279,6 +331,18 @@ class CL_Tracer:
             self.culled_power = [float(v) for v in cp[:n]]
         else:
             self.culled_counts, self.culled_power = [0] * n, [0.0] * n
+
+    def _read_budget(self):
+        """The trace's power budget (read only with the ledger on: the reader
+        waits for the stream)."""
+        self._budget = None
+        if self.engine.budget_on:
+            self._budget = budget_dict(self.engine.budget(), self.culled_counts, self.culled_power)
+
+    def power_budget(self):
+        """The power budget of the last trace (``power_budget=True``), see
+        :func:`budget_dict`; None when the trace ran without it."""
+        return getattr(self, "_budget", None)
 
     def power_culled(self):
         """Total power of the children the cutoff culled in the last trace."""
@@ -336,6 +400,7 @@ class CL_Tracer:
             ph["loop"] = clk() - t_ph
             t_ph = clk()
             self._read_culled()
+            self._read_budget()
         finally:
             self.engine.sync()
         ph["sync"] = clk() - t_ph
