@@ -1,6 +1,8 @@
 // lpc_kernels.hip -- gfx950 kernels of the LightPyCL per-bounce path.
 //
-//   k_packet         per-wave bound (origin ball + direction cone) of 64 or 128 rays.
+//   k_packet         per-wave bound (origin ball + direction cone) of 64 or 128 rays
+//                    (the merged sliver units' bounds of a k_roots_s launch ride
+//                    as extra blocks of it instead: packet_bound).
 //   k_roots*, k_rootwalk, k_spill
 //                    the hot loop (replaces __kernel intersect, .cl:243-289):
 //                    (packet, piece) items whose root test passes, walked one
@@ -549,11 +551,14 @@ static __device__ __forceinline__ uint64_t wave_or64(uint64_t v)
 // read n on the device, nd != NULL).
 // The root tests' records in LDS (cx cy cz negB | negA): the piece loop reads
 // them with broadcast LDS loads instead of one scalar-load round trip per piece.
+// They live in dynamic shared memory sized by the launch's batch (run_queue: 20 B
+// per piece and group record), so a block beside a CU full of walk waves
+// asks for what its table needs, not for a full batch's 21 760 B.
 struct RootsLds {
-    float4 pc[LPC_ROOTS_TASKS * 64];
-    float pa[LPC_ROOTS_TASKS * 64];
-    float4 gc[64];
-    float ga[64];
+    float4 *pc;                         // [npieces]
+    float4 *gc;                         // [ngroups]
+    float *pa;                          // [npieces]
+    float *ga;                          // [ngroups]
 };
 
 template <bool HALF>
@@ -563,16 +568,34 @@ static __device__ __forceinline__ void roots_block(const RaysIn &R, const float 
                                                    int S, int pb, int64_t vb, unsigned long long *s_m,
                                                    uint32_t *s_off, const RootsLds &L);
 
+// pk != NULL (the merged sliver units' packet bounds, LPC_PACKET_FOLD): the
+// launch's blocks from rblocks on run packet_bound<2> instead, one 128-ray packet
+// per wave (k_packet's map and grid-stride); the root tests stride over rblocks.
+// Both ranges only read the population, so neither waits for the other and the
+// bounds need no launch of their own.
 template <bool HALF>
 __global__ __launch_bounds__(256) void k_roots_s(RaysIn R, const float *__restrict__ rs, int64_t n,
                                                  const Piece *__restrict__ pieces, int npieces,
                                                  const Piece *__restrict__ groups, int ngroups, QueueArgs Q,
-                                                 int S, int pb, const long long *__restrict__ nd)
+                                                 int S, int pb, const long long *__restrict__ nd,
+                                                 PacketRec *__restrict__ pk, int rblocks)
 {
     __shared__ unsigned long long s_m[LPC_ROOTS_TASKS];
     __shared__ uint32_t s_off[LPC_ROOTS_TASKS + 1];
-    __shared__ RootsLds L;
+    extern __shared__ float4 s_roots[];
     if (nd) n = *nd;
+    if ((int)blockIdx.x >= rblocks) {
+        const int lane = threadIdx.x & 63;
+        const int64_t stride = (int64_t)(gridDim.x - rblocks) * 4;
+        for (int64_t w = (int64_t)(blockIdx.x - rblocks) * 4 + (threadIdx.x >> 6); w * 128 < n; w += stride)
+            packet_bound<2>(R, rs, n, pk, w, lane);
+        return;
+    }
+    RootsLds L;
+    L.pc = s_roots;
+    L.gc = L.pc + npieces;
+    L.pa = (float *)(L.gc + ngroups);
+    L.ga = L.pa + npieces;
     for (int i = threadIdx.x; i < npieces; i += 256) {
         const Piece &P = pieces[i];
         L.pc[i] = make_float4(P.cx, P.cy, P.cz, P.negB);
@@ -585,7 +608,7 @@ __global__ __launch_bounds__(256) void k_roots_s(RaysIn R, const float *__restri
     }
     __syncthreads();
     const int64_t nvb = ((n + 63) / 64 + pb - 1) / pb;
-    for (int64_t vb = blockIdx.x; vb < nvb; vb += gridDim.x) {
+    for (int64_t vb = blockIdx.x; vb < nvb; vb += rblocks) {
         roots_block<HALF>(R, rs, n, pieces, npieces, groups, ngroups, Q, S, pb, vb, s_m, s_off, L);
         __syncthreads();                          // s_m / s_off reused by the next virtual block
     }
@@ -1767,6 +1790,20 @@ __global__ __launch_bounds__(256) void k_scatter(CompactArgs A)
     }
 }
 
+// The thread index inside a tile body.  OPAQUE (the device-sized kernels' tile
+// loops): the compiler cannot tell it is the same in every tile, so what a tile
+// derives from it is derived in the tile and dies with it.
+#ifndef LPC_DS_TILE_TID
+#define LPC_DS_TILE_TID 1                 // compile-time A/B builds: 0 = the plain thread index
+#endif
+template <bool OPAQUE>
+static __device__ __forceinline__ int tile_tid()
+{
+    int t = (int)threadIdx.x;
+    if constexpr (OPAQUE && LPC_DS_TILE_TID) asm volatile("" : "+v"(t));
+    return t;
+}
+
 // ---------------------------------------------------------------------------
 // Two-kernel compaction of a traced single-chunk iteration (StageArgs /
 // MoveArgs), replacing k_shade + k_count + k_scan + k_scatter + k_append:
@@ -1796,13 +1833,17 @@ __global__ __launch_bounds__(LPC_ST_TILE) void k_shade_stage(StageArgs A)
     __shared__ uint32_t s_bx[LPC_ST_TILE / 64][6];
     __shared__ int32_t s_cc[CUT ? LPC_ST_TILE / 64 : 1];
     __shared__ double s_cp[CUT ? LPC_ST_TILE / 64 : 1];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     // the shading inputs as a local (a device-sized launch sets its n; writing the
     // kernel argument itself would put the whole argument block in scratch)
     ShadeArgs S = A.S;
     if constexpr (DS) S.n = *A.nd;
     auto tile_body = [&](const int64_t tile) {
-    const int64_t r = tile * LPC_ST_TILE + threadIdx.x;
+    // device-sized: the thread index is opaque per tile, so no per-thread address
+    // (one register pair per array) is computed ahead of the tile loop and held
+    // across it; a tile computes them as the one-tile-per-block form does
+    const int tx = tile_tid<DS>();
+    const int lane = tx & 63, wv = tx >> 6;
+    const int64_t r = tile * LPC_ST_TILE + tx;
     const bool in = r < S.n;
     PostOut po;
     po.hit_mesh = -1;
@@ -1891,10 +1932,10 @@ __global__ __launch_bounds__(LPC_ST_TILE) void k_shade_stage(StageArgs A)
     int32_t wo[3] = {0, 0, 0};
     for (int w = 0; w < wv; ++w)
         for (int f = 0; f < 3; ++f) wo[f] += s_w[f][w];
-    if (threadIdx.x < A.nmp) {
+    if (tx < A.nmp) {
         double v = 0.0;
-        for (int k = 0; k < LPC_ST_TILE / 64; ++k) v += s_mp[threadIdx.x][k];
-        A.tmp[tile * LPC_MP_MAX + threadIdx.x] = v;
+        for (int k = 0; k < LPC_ST_TILE / 64; ++k) v += s_mp[tx][k];
+        A.tmp[tile * LPC_MP_MAX + tx] = v;
     }
     const int64_t c = A.cst, t0 = tile * LPC_ST_TILE;
     auto put = [&](float *b, int64_t q, f3 d, float pw) {
@@ -1909,7 +1950,7 @@ __global__ __launch_bounds__(LPC_ST_TILE) void k_shade_stage(StageArgs A)
         A.stM[q] = dest.x; A.stM[c + q] = dest.y; A.stM[2 * c + q] = dest.z; A.stM[3 * c + q] = s.pow;
         ((int32_t *)A.stM)[4 * c + q] = po.hit_mesh;
     }
-    if (threadIdx.x == 0) {
+    if (tx == 0) {
         uint32_t cR = 0, cT = 0, cM = 0;
         double tp = 0.0;                      // fixed order over the tile's waves
         float td = 0.0f;
@@ -1962,7 +2003,6 @@ static __device__ __forceinline__ void stage_move(MoveArgs A)
     __shared__ float s_d[LPC_ST_TILE];
     __shared__ double s_m[LPC_MP_MAX][LPC_ST_TILE];
     __shared__ uint32_t s_b[6][LPC_ST_TILE / 64];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     // device-sized launch (DS): the population size and measured-record length
     // the previous iteration left in A.ctl; grid-stride over the tiles (tile 0's
     // block also publishes an empty iteration's counters)
@@ -1979,6 +2019,7 @@ static __device__ __forceinline__ void stage_move(MoveArgs A)
         m_base = A.ctl->m[A.par];
     }
     auto tile_body = [&](const int64_t tile) {
+    const int t = tile_tid<DS>(), lane = t & 63, wv = t >> 6;     // (opaque per tile: see k_shade_stage)
     // this tile's prefix and the totals: the group counts (the groups before this
     // tile's, all groups), then this group's tiles before it
     long long pre[3] = {0, 0, 0}, tot[3] = {0, 0, 0};

@@ -187,6 +187,11 @@ struct Knobs {
     bool spec = true;                               // LPC_SPEC: speculative iterations (trace_run)
     bool bsort = true;                              // LPC_BSORT: 0 = the emitted rays sort by rocPRIM even where the
                                                     //   counting sort fits (A/B and test hook; the order is the same)
+    bool packet_fold = true;                        // LPC_PACKET_FOLD: the merged sliver units' packet bounds as extra
+                                                    //   blocks of the k_roots_s launch; 0 = k_packet, a launch of its
+                                                    //   own (A/B and test hook; the same PacketRec bits)
+    bool roots_lds = true;                          // LPC_ROOTS_LDS: k_roots_s asks for the LDS its batch's records
+                                                    //   need; 0 = for a full batch's (A/B hook)
     double dcap_init = 16.0;                        // LPC_DCAP_MILLI / 1000 (tests: a rebuild inside a trace)
     int spill_budget = 20;                          // LPC_BUDGET: node visits before a wave hands its work over (0 off)
     int64_t spill_large_per_tri = 16;               // LPC_LARGE_PER_TRI
@@ -958,25 +963,36 @@ static int run_queue(lpc_handle *h, const RaysIn &in, const float *rs, int64_t n
         fprintf(stderr, "[lpc host] roots: n %lld packets %lld pieces %d groups %d S %d pb %d blocks %lld rcap %lld\n",
                 (long long)n, (long long)sh.npk, (int)pt->npieces, (int)pt->ngroups, sh.rs_S, sh.rs_pb,
                 (long long)sh.rs_blocks, (long long)Q.rcap);
+    // merged sliver tests (LPC_SLIVER_MERGE): the packet bounds before the walk,
+    // on this stream; the walk's waves take the (packet group, piece) units.
+    // The bounds are ceil(npkx / 4) more blocks of the first k_roots_s launch
+    // (LPC_PACKET_FOLD); k_packet where there is none (k_gather_roots wrote the
+    // items: folded in there it was slower) or the knob is off
+    const int64_t npkx = (n + 127) / 128;
+    const bool fold = merged && !roots_done && h->knobs.packet_fold;
     for (int k = 0; !roots_done && k < sh.nbatch; ++k) {
         const int32_t np = std::min<int32_t>(pt->npieces - k * LPC_ROOTS_BATCH, LPC_ROOTS_BATCH);
         const RootsBatch b = roots_batch(sh.npk, ds, np);
         const Piece *pc = (const Piece *)pt->pieces.p + (size_t)k * LPC_ROOTS_BATCH;
-        const dim3 rg((unsigned)std::max<int64_t>(b.blocks, 1));
+        const int64_t rblocks = std::max<int64_t>(b.blocks, 1);
+        const int64_t pblocks = (fold && k == 0) ? (npkx + 3) / 4 : 0;
+        const dim3 rg((unsigned)(rblocks + pblocks));
+        // the records' LDS: 20 B per piece and group of this batch
+        const size_t lds = (size_t)20 * (h->knobs.roots_lds ? (size_t)np + (size_t)pt->ngroups
+                                                             : (size_t)LPC_ROOTS_BATCH + 64);
         with_bool(half, [&](auto hf) {
-            hipLaunchKernelGGL(k_roots_s<decltype(hf)::value>, rg, dim3(256), 0, h->stream, in, rs, n, pc, (int)np,
-                               (const Piece *)pt->groups.p, (int)pt->ngroups, Q, b.S, b.pb, ds ? ds->nd : nullptr);
+            hipLaunchKernelGGL(k_roots_s<decltype(hf)::value>, rg, dim3(256), lds, h->stream, in, rs, n, pc, (int)np,
+                               (const Piece *)pt->groups.p, (int)pt->ngroups, Q, b.S, b.pb, ds ? ds->nd : nullptr,
+                               pblocks ? (PacketRec *)h->w_pk.p : nullptr, (int)rblocks);
         });
     }
-    // merged sliver tests (LPC_SLIVER_MERGE): the packet bounds before the walk,
-    // on this stream; the walk's waves take the (packet group, piece) units
     SliverArgs SA;
     memset(&SA, 0, sizeof(SA));
     if (merged) {
         SA = *merged;
-        const int64_t npkx = (n + 127) / 128;
-        hipLaunchKernelGGL(k_packet<2>, dim3((unsigned)((npkx + 3) / 4)), dim3(256), 0, h->stream, in, rs, n,
-                           (PacketRec *)h->w_pk.p, ds ? ds->nd : nullptr);
+        if (!fold)
+            hipLaunchKernelGGL(k_packet<2>, dim3((unsigned)((npkx + 3) / 4)), dim3(256), 0, h->stream, in, rs, n,
+                               (PacketRec *)h->w_pk.p, ds ? ds->nd : nullptr);
     }
     RayBase ray;
     RETIF(ray_base(h, in, rs, n, &ray));
@@ -1423,6 +1439,8 @@ int lpc_open(int device, lpc_handle **out)
     k.walk_grid = std::min<int64_t>(std::max<int64_t>(env_int("LPC_WALK_GRID", k.walk_grid), 64), 1 << 22);
     k.spec = env_int("LPC_SPEC", k.spec) != 0;
     k.bsort = env_int("LPC_BSORT", k.bsort) != 0;
+    k.packet_fold = env_int("LPC_PACKET_FOLD", k.packet_fold) != 0;
+    k.roots_lds = env_int("LPC_ROOTS_LDS", k.roots_lds) != 0;
     k.dcap_init = (double)env_int("LPC_DCAP_MILLI", 16000) / 1000.0;
     k.spill_budget = (int)env_int("LPC_BUDGET", k.spill_budget);
     k.spill_large_per_tri = env_int("LPC_LARGE_PER_TRI", k.spill_large_per_tri);
