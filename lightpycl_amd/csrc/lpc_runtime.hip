@@ -43,21 +43,23 @@ static double host_us()
 
 namespace {
 
-// 8 SoA arrays (ox oy oz dx dy dz pw | pmid) in one allocation.
+// 8 SoA arrays (ox oy oz dx dy dz pw | pmid), st floats apart from f, as a RaysIn / RaysOut
+template <class R, class F> static R soa_rows(F *f, int64_t st)
+{
+    R r;
+    r.ox = f; r.oy = f + st; r.oz = f + 2 * st; r.dx = f + 3 * st; r.dy = f + 4 * st; r.dz = f + 5 * st;
+    r.pw = f + 6 * st; r.pmid = (decltype(r.pmid))(f + 7 * st);
+    return r;
+}
+
+// ... in one allocation.
 struct Pop {
     DBuf buf;
     int64_t cap = 0;
     float *f(int k) const { return (float *)buf.p + (size_t)k * cap; }
-    int32_t *pmid() const { return (int32_t *)((float *)buf.p + (size_t)7 * cap); }
-    template <class R> R rows(int64_t off) const {
-        R r;
-        r.ox = f(0) + off; r.oy = f(1) + off; r.oz = f(2) + off;
-        r.dx = f(3) + off; r.dy = f(4) + off; r.dz = f(5) + off;
-        r.pw = f(6) + off; r.pmid = pmid() + off;
-        return r;
-    }
-    RaysIn in(int64_t off = 0) const { return rows<RaysIn>(off); }
-    RaysOut out(int64_t off = 0) const { return rows<RaysOut>(off); }
+    int32_t *pmid() const { return (int32_t *)f(7); }
+    RaysIn in(int64_t off = 0) const { return soa_rows<RaysIn>((const float *)f(0) + off, cap); }
+    RaysOut out(int64_t off = 0) const { return soa_rows<RaysOut>(f(0) + off, cap); }
 };
 
 struct PieceTable {
@@ -198,11 +200,35 @@ struct Knobs {
     int64_t spill_cap = (int64_t)1 << 22;           // LPC_SPILL_CAP: k_spill queue capacity (items)
     int host_prof = 0;                              // LPC_HOSTPROF: host-side timing of each iteration (stderr);
                                                     //   2: also each launch's hand-over queue lengths (synchronising)
-    int stage_mode = 0;                             // LPC_STAGE_MODE: 0 pageable DMA (round 6 A/B: 1.23-1.28 G fresh
-                                                    //   rays), 1 pinned rows (0.83-0.93), 2 pinned SoA chunks (0.77-1)
     int map_slices = 6;                             // LPC_MAP_SLICES: k_map_hist keeps the map in LDS while it fits this
                                                     //   many slices (one sweep each); 0 = always global atomics
     int map_per_cu = 8;                             // LPC_MAP_PER_CU: its blocks per CU on the global-atomic paths
+};
+
+// What the last launch left in the slot arrays and the launch words.  ensure_ws
+// assigns it whole (fresh arrays: nothing is clean), run_intersect takes it by
+// value and clears it, enqueue_fused_chunk assigns it whole at its end.
+struct SlotState {
+    bool clean = false;                             // every slot is (max_ray_len mrl, idx -1, count 0)
+    float mrl = 0.0f;
+    bool misc_clean = false;                        // the launch words were reset for the next launch
+};
+
+// The per 256-tile group counts: two buffers of `cap` words in w_gsum, zero when
+// unused.  A traced launch adds into the first ng groups of buffer `par` (word
+// offset cur) while its k_stage_move zeroes the dirty_next groups the launch
+// before left in the other (offset next); then the buffers swap roles.
+struct GroupWords {
+    int64_t cap = 0;
+    int par = 0;
+    int64_t dirty[2] = {0, 0};
+    struct Turn { size_t cur, next; int64_t dirty_next; };
+    Turn turn(int64_t ng)
+    {
+        const Turn t{(size_t)par * (size_t)cap, (size_t)(1 - par) * (size_t)cap, dirty[1 - par]};
+        dirty[1 - par] = 0; dirty[par] = ng; par = 1 - par;
+        return t;
+    }
 };
 
 // Every GPU resource of the handle is held by an owner of lpc_resource.hpp and
@@ -227,18 +253,12 @@ struct lpc_handle {
     DBuf w_aos;                                     // rays as 32-byte rows for the coherence gather
     DBuf w_tm;                                      // per ray: the slots a flush wrote (traced path, K <= 32)
     DBuf w_bhist;                                   // its per-block hi-digit counts + digit totals
-    bool acc_pending = false;                       // next slot reset also resets the iteration counters
-    int64_t acc_pending_total = 0;
     int64_t m_inflight = 0;                         // populations of the iterations enqueued, not yet read
     DBuf w_fc;                                      // k_shade_stage tile counts / power / max |dir|^2
-    DBuf w_gsum;                                    // per 256-tile group counts, two buffers (zero when unused)
-    int64_t gcap = 0;
-    int gpar = 0;                                   // the buffer the next traced launch uses
-    int64_t gdirty[2] = {0, 0};                     // groups a launch left non-zero in each buffer
-    bool slots_clean = false;                       // every slot (max_ray_len slots_mrl, idx -1, count 0)
-    float slots_mrl = 0.0f;
-    bool misc_clean = false;                        // the launch words were reset for the next launch
-    DBuf w_pk;                                      // PacketRec per 128-ray wave (k_slivers)
+    DBuf w_gsum;                                    // per 256-tile group counts (GroupWords)
+    GroupWords groups;
+    SlotState slots;                                // w_key / w_sc / d_misc as the last launch left them
+    DBuf w_pk;                                     // PacketRec per 128-ray wave (k_slivers)
     DBuf d_misc;                                    // LPC_MISC_WORDS per-launch words
     size_t sort_tmp_bytes = 0;
     DBuf w_spill;                                   // k_spill queue
@@ -250,7 +270,6 @@ struct lpc_handle {
     // device-sized (IterCtl) before iteration i's counters are read
     DBuf d_ctl;                                     // IterCtl
     int ctl_par = 0;                                // the parity the next enqueued iteration reads
-    double ds_thr = -INFINITY;                      // trace_run's power threshold (k_stage_move's stop rule)
     std::vector<double> hist_r;                     // the last trace_run's populations / its first (the
     int32_t hist_iter = -1;                         //   speculation's prediction) and its iteration limit
     bool dcap_rebuilt = false;                      // check_dcap rebuilt the records (a speculative iteration is void)
@@ -323,8 +342,7 @@ struct lpc_handle {
     // thread on the copy stream while the handle traces the batch before it
     struct RaySlot {
         Pop P;                                      // the batch as SoA rows (swapped with I when it is traced)
-        DBuf aos;                                   // its (n,4) origin / direction rows (stage modes 0, 1)
-        Pinned<void> pin;                           // pinned host staging of the caller's rows
+        DBuf aos;                                   // its (n,4) origin / direction rows
         DBuf scan;                                  // k_ray_scan of the batch (device) ...
         Pinned<RayScan> scan_host;                  // ... and its pinned copy
         Event ev;                                   // the batch's copies, unpacks and scan done (cstream)
@@ -688,13 +706,12 @@ static int ensure_ws(lpc_handle *h, int64_t n)
         const int64_t nt = (C + LPC_ST_TILE - 1) / LPC_ST_TILE;
         RETIF(dalloc(h, h->w_fc, (size_t)nt * (8 + 4 + 4 + 8 * LPC_MP_MAX) + 64));   // staging tiles' power, counts,
                                                                                       // max |dir|^2, measured power
-        h->gcap = (nt + LPC_ST_GROUP - 1) / LPC_ST_GROUP + 1;                        // group counts, two launches'
-        RETIF(dalloc(h, h->w_gsum, (size_t)2 * h->gcap * 8));
+        GroupWords gw;                                                                // group counts, two launches'
+        gw.cap = (nt + LPC_ST_GROUP - 1) / LPC_ST_GROUP + 1;
+        RETIF(dalloc(h, h->w_gsum, (size_t)2 * gw.cap * 8));
         HIPCHK(h, hipMemsetAsync(h->w_gsum.p, 0, h->w_gsum.bytes, h->stream));
-        h->gpar = 0;
-        h->gdirty[0] = h->gdirty[1] = 0;
-
-        h->slots_clean = h->misc_clean = false;         // fresh slot arrays
+        h->groups = gw;                                 // all zero: buffer 0 first, nothing dirty
+        h->slots = SlotState();                         // fresh slot arrays
         h->sort_tmp_bytes = tb;
         h->ws_rays = C;
     }
@@ -758,11 +775,27 @@ struct DevSize {
     int64_t bound;              // capacity bound: workspaces, root-item shards
 };
 
-// Work hand-over (k_spill levels): queue, budget by population size.  tmask:
-// the launch's written-slot masks (run_intersect), or NULL.
-static int spill_setup(lpc_handle *h, int64_t n, uint32_t *tmask, SpillArgs *SP)
+// One intersect launch: what all its stages share.  run_intersect builds it once
+// (rs / perm once the coherence order is made); the stages take it whole.
+struct Launch {
+    RaysIn in;                          // the rays where the caller holds them ...
+    const float *rs = nullptr;          // ... and their coherence copy (8 arrays of stride n), or NULL
+    int64_t n = 0;                      // rays (device-sized: the expected size, which shapes the launches)
+    const int32_t *perm = nullptr;      // ray index of a position in the coherence order, or NULL (identity)
+    float eps = 0.0f, max_ray_len = 0.0f;
+    unsigned long long *skey = nullptr, *stats = nullptr;   // the slot arrays; profiling: the walk counters, or NULL
+    int32_t *scnt = nullptr;
+    const DevSize *ds = nullptr;
+    uint32_t *tmask = nullptr;          // the launch's written-slot masks, or NULL
+    bool half = false;                  // the half-line cull at the piece roots
+    PieceTable *pt = nullptr;           // the pieces of its root items
+    const long long *nd() const { return ds ? ds->nd : nullptr; }
+};
+
+// Work hand-over (k_spill levels): queue, budget by population size.
+static int spill_setup(lpc_handle *h, const Launch &L, SpillArgs *SP)
 {
-    *SP = SpillArgs{nullptr, nullptr, 0u, 0, 31, tmask, nullptr};
+    *SP = SpillArgs{nullptr, nullptr, 0u, 0, 31, L.tmask, nullptr};
     if (h->prof.stats) {                // diagnostic: the fan triangles (apex valence >= 32), built once
         if (!h->scene.d_fan.p) {
             RETIF(host_vertices(h));
@@ -790,7 +823,7 @@ static int spill_setup(lpc_handle *h, int64_t n, uint32_t *tmask, SpillArgs *SP)
     SP->cap = (uint32_t)std::min<int64_t>(h->knobs.spill_cap, 0x7fffffff);
     // no hand-over once a population fills the chip many times over (from
     // LPC_LARGE_PER_TRI rays per triangle)
-    SP->budget = n >= h->knobs.spill_large_per_tri * (int64_t)h->scene.M ? 0 : h->knobs.spill_budget;
+    SP->budget = L.n >= h->knobs.spill_large_per_tri * (int64_t)h->scene.M ? 0 : h->knobs.spill_budget;
     SP->pair_shift = kSpillPairShift;
     return 0;
 }
@@ -798,9 +831,10 @@ static int spill_setup(lpc_handle *h, int64_t n, uint32_t *tmask, SpillArgs *SP)
 // The rays of a launch as one base of 8 equally spaced arrays (RayBase): the
 // coherence copy (stride n) or a population / staging buffer (stride = its
 // capacity).  Every RaysIn the runtime builds has this shape.
-static int ray_base(lpc_handle *h, const RaysIn &in, const float *rs, int64_t n, RayBase *out)
+static int ray_base(lpc_handle *h, const Launch &L, RayBase *out)
 {
-    if (rs) { *out = RayBase{rs, n}; return 0; }
+    if (L.rs) { *out = RayBase{L.rs, L.n}; return 0; }
+    const RaysIn &in = L.in;
     const int64_t st = in.oy - in.ox;
     if (in.oz - in.oy != st || in.dx - in.oz != st || in.dy - in.dx != st || in.dz - in.dy != st)
         return set_err(h, LPC_E_ARG, "internal: ray arrays not equally spaced");
@@ -829,13 +863,11 @@ static void spill_level_args(lpc_handle *h, const SpillArgs &SP, int l, int leve
 
 // hand-over levels: level l reads queue l % 2 (length misc[6 + l]) and queues
 // what exceeds the budget for level l + 1; the last level finishes
-static int run_spill_levels(lpc_handle *h, const RaysIn &in, const float *rs, int64_t n, const int32_t *perm,
-                            float eps, float max_ray_len, unsigned long long *skey, int32_t *scnt,
-                            unsigned long long *stats, const SpillArgs &SP, const long long *nd = nullptr)
+static int run_spill_levels(lpc_handle *h, const Launch &L, const SpillArgs &SP)
 {
     RayBase ray;
-    RETIF(ray_base(h, in, rs, n, &ray));
-    const int levels = spill_level_count(h, n, SP);
+    RETIF(ray_base(h, L, &ray));
+    const int levels = spill_level_count(h, L.n, SP);
     for (int l = 0; l < levels; ++l) {
         SpillArgs I, O;
         spill_level_args(h, SP, l, levels, &I, &O);
@@ -843,10 +875,10 @@ static int run_spill_levels(lpc_handle *h, const RaysIn &in, const float *rs, in
         // 4-wave units, launched as single-wave blocks
         const unsigned g = (unsigned)std::max<int64_t>(kSpillMinBlocks, kSpillBlocks >> l) * 4u;
         // profiling counters only in the PROF instantiation (fewer live registers without)
-        with_bool(stats != nullptr, [&](auto pf) {
-            hipLaunchKernelGGL((k_spill<8, decltype(pf)::value>), dim3(g), dim3(64), 0, h->stream, ray, n, perm,
-                               (const Node8 *)h->scene.d_nodes.p, (const ExactRec *)h->scene.d_xrec.p, eps,
-                               max_ray_len, skey, scnt, stats, I, O, nd);
+        with_bool(L.stats != nullptr, [&](auto pf) {
+            hipLaunchKernelGGL((k_spill<8, decltype(pf)::value>), dim3(g), dim3(64), 0, h->stream, ray, L.n, L.perm,
+                               (const Node8 *)h->scene.d_nodes.p, (const ExactRec *)h->scene.d_xrec.p, L.eps,
+                               L.max_ray_len, L.skey, L.scnt, L.stats, I, O, L.nd());
         });
     }
     HIPCHK(h, hipGetLastError());
@@ -909,11 +941,12 @@ struct QueueShape {
     int rs_S, rs_pb;
     int nbatch;                                 // k_roots_s launches (pieces in batches of LPC_ROOTS_BATCH)
 };
-static int queue_args(lpc_handle *h, int64_t n, const PieceTable *pt, const DevSize *ds, QueueArgs *Qo,
-                      QueueShape *sh)
+static int queue_args(lpc_handle *h, const Launch &L, QueueArgs *Qo, QueueShape *sh)
 {
+    const PieceTable *pt = L.pt;
+    const DevSize *ds = L.ds;
     // device-sized (ds): n is the expected size (grids), the bound sizes the shards
-    const int64_t npk = (n + 63) / 64;
+    const int64_t npk = (L.n + 63) / 64;
     const int nbatch = std::max(1, (int)((pt->npieces + LPC_ROOTS_BATCH - 1) / LPC_ROOTS_BATCH));
     if (nbatch > 1 && pt->ngroups > 0) return set_err(h, LPC_E_STATE, "internal: gated pieces in several batches");
     const RootsBatch b0 = roots_batch(npk, ds, std::min<int32_t>(pt->npieces, LPC_ROOTS_BATCH));
@@ -926,39 +959,30 @@ static int queue_args(lpc_handle *h, int64_t n, const PieceTable *pt, const DevS
         const RootsBatch b = roots_batch(npk, ds, np);
         rcap += ((b.vblocks + LPC_Q_CSHARDS - 1) / LPC_Q_CSHARDS) * b.pb * (int64_t)np;
     }
-    const int rs_S = b0.S, rs_pb = b0.pb;
-    const int64_t rs_blocks = b0.blocks;
     // k_gather_roots: one packet per wave of its blocks
     const int64_t gpb = LPC_GR_T / 64;
     rcap = std::max<int64_t>(rcap, ((((npk + gpb - 1) / gpb) + LPC_Q_CSHARDS - 1) / LPC_Q_CSHARDS) * gpb *
                                        (int64_t)pt->npieces);
     if (rcap >= 0xffffffffLL) return set_err(h, LPC_E_ARG, "root items: too many per shard");
     RETIF(dalloc(h, h->w_qroots, (size_t)LPC_Q_CSHARDS * (size_t)rcap * 8));
-    QueueArgs Q;
-    Q.roots = (uint64_t *)h->w_qroots.p;
-    Q.ctl = (uint32_t *)h->d_misc.p;
-    Q.err = (uint32_t *)((char *)h->d_acc.p + offsetof(DevAcc, qerr));
-    Q.rcap = (uint32_t)rcap;
-    *Qo = Q;
-    sh->npk = npk; sh->rs_blocks = rs_blocks; sh->rs_S = rs_S; sh->rs_pb = rs_pb;
-    sh->nbatch = nbatch;
+    *Qo = QueueArgs{(uint64_t *)h->w_qroots.p, (uint32_t *)h->d_misc.p,
+                    (uint32_t *)((char *)h->d_acc.p + offsetof(DevAcc, qerr)), (uint32_t)rcap};
+    *sh = QueueShape{npk, b0.blocks, b0.S, b0.pb, nbatch};
     return 0;
 }
 
 // The hierarchy stage: k_roots_s writes the (packet, piece) items whose root test
 // passes, k_rootwalk walks them grid-stride and hands heavy subtrees to the
-// k_spill levels.  half: the half-line cull at the piece
-// roots; tmask: the launch's written-slot masks or NULL (both run_intersect's).
-// roots_done: k_gather_roots already wrote the items (same queue arguments).
-// *sampled: the walk launch carries profiling events.
-static int run_queue(lpc_handle *h, const RaysIn &in, const float *rs, int64_t n, const int32_t *perm,
-                     const PieceTable *pt, float eps, float max_ray_len, unsigned long long *skey, int32_t *scnt,
-                     unsigned long long *stats, const DevSize *ds, const SliverArgs *merged, bool roots_done,
-                     bool half, uint32_t *tmask, bool *sampled)
+// k_spill levels.  merged: the sliver units of the walk's
+// tail, or NULL.  roots_done: k_gather_roots already wrote the items (same queue
+// arguments).  *sampled: the walk launch carries profiling events.
+static int run_queue(lpc_handle *h, const Launch &L, const SliverArgs *merged, bool roots_done, bool *sampled)
 {
+    const int64_t n = L.n;
+    const PieceTable *pt = L.pt;
     QueueArgs Q;
     QueueShape sh;
-    RETIF(queue_args(h, n, pt, ds, &Q, &sh));
+    RETIF(queue_args(h, L, &Q, &sh));
     if (h->knobs.host_prof)
         fprintf(stderr, "[lpc host] roots: n %lld packets %lld pieces %d groups %d S %d pb %d blocks %lld rcap %lld\n",
                 (long long)n, (long long)sh.npk, (int)pt->npieces, (int)pt->ngroups, sh.rs_S, sh.rs_pb,
@@ -972,7 +996,7 @@ static int run_queue(lpc_handle *h, const RaysIn &in, const float *rs, int64_t n
     const bool fold = merged && !roots_done && h->knobs.packet_fold;
     for (int k = 0; !roots_done && k < sh.nbatch; ++k) {
         const int32_t np = std::min<int32_t>(pt->npieces - k * LPC_ROOTS_BATCH, LPC_ROOTS_BATCH);
-        const RootsBatch b = roots_batch(sh.npk, ds, np);
+        const RootsBatch b = roots_batch(sh.npk, L.ds, np);
         const Piece *pc = (const Piece *)pt->pieces.p + (size_t)k * LPC_ROOTS_BATCH;
         const int64_t rblocks = std::max<int64_t>(b.blocks, 1);
         const int64_t pblocks = (fold && k == 0) ? (npkx + 3) / 4 : 0;
@@ -980,9 +1004,9 @@ static int run_queue(lpc_handle *h, const RaysIn &in, const float *rs, int64_t n
         // the records' LDS: 20 B per piece and group of this batch
         const size_t lds = (size_t)20 * (h->knobs.roots_lds ? (size_t)np + (size_t)pt->ngroups
                                                              : (size_t)LPC_ROOTS_BATCH + 64);
-        with_bool(half, [&](auto hf) {
-            hipLaunchKernelGGL(k_roots_s<decltype(hf)::value>, rg, dim3(256), lds, h->stream, in, rs, n, pc, (int)np,
-                               (const Piece *)pt->groups.p, (int)pt->ngroups, Q, b.S, b.pb, ds ? ds->nd : nullptr,
+        with_bool(L.half, [&](auto hf) {
+            hipLaunchKernelGGL(k_roots_s<decltype(hf)::value>, rg, dim3(256), lds, h->stream, L.in, L.rs, n, pc, (int)np,
+                               (const Piece *)pt->groups.p, (int)pt->ngroups, Q, b.S, b.pb, L.nd(),
                                pblocks ? (PacketRec *)h->w_pk.p : nullptr, (int)rblocks);
         });
     }
@@ -991,13 +1015,13 @@ static int run_queue(lpc_handle *h, const RaysIn &in, const float *rs, int64_t n
     if (merged) {
         SA = *merged;
         if (!fold)
-            hipLaunchKernelGGL(k_packet<2>, dim3((unsigned)((npkx + 3) / 4)), dim3(256), 0, h->stream, in, rs, n,
-                               (PacketRec *)h->w_pk.p, ds ? ds->nd : nullptr);
+            hipLaunchKernelGGL(k_packet<2>, dim3((unsigned)((npkx + 3) / 4)), dim3(256), 0, h->stream, L.in, L.rs, n,
+                               (PacketRec *)h->w_pk.p, L.nd());
     }
     RayBase ray;
-    RETIF(ray_base(h, in, rs, n, &ray));
+    RETIF(ray_base(h, L, &ray));
     SpillArgs SP;
-    RETIF(spill_setup(h, n, tmask, &SP));
+    RETIF(spill_setup(h, L, &SP));
     const unsigned grid = (unsigned)h->knobs.walk_grid;      // single-wave blocks
     // profiling: the launch's own start/stop timestamps (hipExtLaunchKernel), no
     // event packets between the kernels
@@ -1009,16 +1033,16 @@ static int run_queue(lpc_handle *h, const RaysIn &in, const float *rs, int64_t n
     // profiling counters only in the PROF instantiation, the merged sliver units
     // only in the MERGED one (fewer live registers without: the plain walk holds
     // 7 waves per SIMD, the merged one 6)
-    with_bool(stats != nullptr, [&](auto pf) {
+    with_bool(L.stats != nullptr, [&](auto pf) {
         with_bool(merged != nullptr, [&](auto mg) {
             hipExtLaunchKernelGGL((k_rootwalk<8, decltype(pf)::value, decltype(mg)::value>), dim3(grid), dim3(64), 0,
-                                  h->stream, k0, k1, 0, ray, n, perm, (const Node8 *)h->scene.d_nodes.p,
-                                  (const ExactRec *)h->scene.d_xrec.p, eps, max_ray_len, skey, scnt, stats, Q, SP,
-                                  ds ? ds->nd : nullptr, SA);
+                                  h->stream, k0, k1, 0, ray, n, L.perm, (const Node8 *)h->scene.d_nodes.p,
+                                  (const ExactRec *)h->scene.d_xrec.p, L.eps, L.max_ray_len, L.skey, L.scnt, L.stats,
+                                  Q, SP, L.nd(), SA);
         });
     });
     if (*sampled) h->prof.ev_kern.emplace_back(std::move(k0), std::move(k1));
-    RETIF(run_spill_levels(h, in, rs, n, perm, eps, max_ray_len, skey, scnt, stats, SP, ds ? ds->nd : nullptr));
+    RETIF(run_spill_levels(h, L, SP));
     if (h->knobs.host_prof >= 2) {                          // diagnostic: this launch's hand-over queue lengths
         uint32_t q[8] = {0};
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1048,7 +1072,8 @@ static bool side_stream(lpc_handle *h)
 }
 
 // One intersect launch's inputs and outputs (run_intersect).  The drop-in calls
-// leave trace / traced / ds at their defaults: no cull, no masks.
+// leave trace / traced / ds / acc_reset at their defaults: no cull, no masks,
+// the iteration counters untouched.
 struct IsectIn {
     RaysIn rays;
     int64_t n = 0;
@@ -1059,12 +1084,199 @@ struct IsectIn {
     const DevSize *ds = nullptr;
     bool trace = false;                             // an iteration of the trace, over its population ...
     bool traced = false;                            // ... without per-ray exports
+    bool acc_reset = false;                         // the launch's slot reset also resets the iteration counters,
+    int64_t acc_total = 0;                          //   to this measured total (iter_enqueue, a one-chunk iteration)
 };
 struct IsectOut {
     RaysIn traced;                                  // IsectIn::traced: the rays in the launch's order
     uint32_t *tmask = nullptr;                      // this launch's written-slot masks (k_shade_stage reads them)
     bool sampled = false;                           // the walk launch carries profiling events
 };
+
+// ---- the other stages of one intersect launch, in launch order (run_intersect) ----
+// The piece cut: q_level's (the same sliver pieces at every cut), coarser while
+// k_roots_s cannot hold the pieces (tiny populations; a table of more than 1 024
+// run roots, g = 1, goes to k_roots_s in batches).
+static int piece_cut(lpc_handle *h, int64_t n, bool chained, PieceTable **pt)
+{
+    int32_t g = q_level(h, n, chained);
+    RETIF(piece_table(h, pt, g));
+    while ((*pt)->npieces > LPC_ROOTS_BATCH && g > 1) {
+        g = std::max(1, g / 8);
+        RETIF(piece_table(h, pt, g));
+    }
+    return 0;
+}
+
+// The slot / launch-word reset; returns the SlotInit the key kernel is to carry.
+// Traced iterations (k_shade_stage) leave every slot they read in the clean state
+// (max_ray_len, idx -1, count 0) and k_stage_move resets the launch words for the
+// next launch, so a traced launch after one (`was`) resets less; where the key
+// kernel runs before everything that reads the launch words (fold), it carries the
+// reset.  "counters": the iteration counters too, where a.acc_reset asks (with
+// clean slots never: k_stage_move writes every counter).
+//   traced  slots clean  fold  words clean | k_slot_init launched here           | the key kernel carries
+//   yes     no           -     -           | whole array, masks, words, counters | -
+//   yes     yes          yes   -           | -                                   | words
+//   yes     yes          no    no          | words                               | -
+//   yes     yes          no    yes         | -                                   | -
+//   no      -            yes   -           | -                                   | n rays' slots, words, counters
+//   no      -            no    -           | n rays' slots, words, counters      | -
+static SlotInit slot_reset(lpc_handle *h, const Launch &L, const IsectIn &a, bool fold, SlotState was)
+{
+    SlotInit SI;
+    SI.K = h->scene.K; SI.live = (const int32_t *)h->scene.d_live.p; SI.max_ray_len = L.max_ray_len;
+    SI.skey = L.skey; SI.scnt = L.scnt; SI.misc = (uint32_t *)h->d_misc.p;
+    SI.acc = a.acc_reset ? (DevAcc *)h->d_acc.p : nullptr;
+    SI.m_total = (unsigned long long)a.acc_total;
+    SI.uniform = 0; SI.tmask = nullptr;
+    SlotInit none = SI;
+    none.skey = nullptr; none.misc = nullptr; none.acc = nullptr;
+    auto launch = [&](int64_t rays) {
+        hipLaunchKernelGGL(k_slot_init, dim3(grid1(std::max<int64_t>(rays, LPC_MISC_WORDS))), dim3(256), 0, h->stream,
+                           rays, SI);
+    };
+    const bool clean = a.traced && was.clean && was.mrl == L.max_ray_len;
+    if (a.traced && !clean) {           // the whole array to the clean state (stride-independent)
+        SI.uniform = 1;
+        SI.tmask = (uint32_t *)h->w_tm.p;
+        launch(h->ws_rays);
+        return none;
+    }
+    if (clean) { SI.skey = nullptr; SI.acc = nullptr; }     // the launch words only
+    if (fold) return SI;
+    if (!(clean && was.misc_clean)) launch(clean ? 0 : L.n);
+    return none;
+}
+
+// The coherence order of a launch of at least kSortMin rays: rays of one wave
+// share origin cell and direction (key [scene-box origin cell | direction]),
+// sorted by the counting sort or rocPRIM, then gathered from the 32-byte rows the
+// key kernel wrote -- with the root tests fused in (k_gather_roots) when the
+// launch has one root-test task per packet and no run gate (roots_done: it wrote
+// the root items).  SIk: slot_reset's.
+struct Order { const float *rs = nullptr; const int32_t *perm = nullptr; bool roots_done = false; };
+static int coherence_order(lpc_handle *h, const Launch &L, const IsectIn &a, const SlotInit &SIk, Order *out)
+{
+    const RaysIn &in = L.in;
+    const int64_t n = L.n;
+    const bool traced = a.traced;
+    const float *blo = h->scene.box_lo, *bsc = h->scene.box_scale;     // the coherence key's box
+    const size_t C = (size_t)h->ws_rays;
+    uint32_t *kin = (uint32_t *)h->w_sort.p, *kout = kin + C;
+    int32_t *vin = (int32_t *)(kout + C), *vout = vin + C;
+    // the emitted rays' varying key bits (set_rays)
+    int b0 = 0, b1 = 32;
+    if (traced && h->pop.emitted) { b0 = h->emitted.init_key_lo; b1 = h->emitted.init_key_hi; }
+    const int nbits = b1 - b0;
+    if (traced && h->pop.emitted && h->emitted.init_bsort && h->knobs.bsort && nbits >= 1 && nbits <= 16 &&
+        n >= LPC_MISC_WORDS) {
+        // counting sort (MSD, two 8-bit digits, stable), then the gather
+        const int hb = std::min(nbits, LPC_BS_HB), lb = nbits - hb;
+        const int64_t nblk = (n + LPC_BS_RPB - 1) / LPC_BS_RPB;
+        uint32_t *hist = (uint32_t *)h->w_bhist.p, *tot = hist + (size_t)LPC_BS_ND * nblk;
+        uint32_t *bst = tot + LPC_BS_ND;
+        hipLaunchKernelGGL(k_bkey, dim3((unsigned)nblk), dim3(LPC_BS_T), 0, h->stream, in, n, blo[0], blo[1],
+                           blo[2], bsc[0], bsc[1], bsc[2], kin, (float4 *)h->w_aos.p, SIk, b0, lb, hb, hist, nblk);
+        hipLaunchKernelGGL(k_bprefix, dim3(1u << hb), dim3(256), 0, h->stream, hist, nblk, tot);
+        hipLaunchKernelGGL(k_bscatter, dim3((unsigned)nblk), dim3(LPC_BS_T), 0, h->stream, (const uint32_t *)kin,
+                           n, b0, lb, hb, (const uint32_t *)hist, nblk, (const uint32_t *)tot, bst,
+                           (uint8_t *)kout, vin, vout);
+        if (lb > 0)
+            hipLaunchKernelGGL(k_bsort2, dim3(1u << hb, LPC_BS_MAXB / LPC_BS_RPB), dim3(LPC_BS_T), 0, h->stream,
+                               (const uint8_t *)kout, (const int32_t *)vin, lb, (const uint32_t *)bst, vout);
+    } else {
+        // a re-sorted chained population: the key (5-D Morton) spans its own box
+        // (k_stage_move of the iteration that made it), not the scene's
+        const uint32_t *pbox = (traced && h->pop.traced && h->pop.pbox_ok) ? (const uint32_t *)h->d_pbox.p : nullptr;
+        hipLaunchKernelGGL(k_raykey, dim3(grid1(n)), dim3(256), 0, h->stream, in, n, blo[0], blo[1], blo[2], bsc[0],
+                           bsc[1], bsc[2], kin, vin, (float4 *)h->w_aos.p, SIk, pbox, pbox ? kKeyObits : 5,
+                           pbox ? 1 : 0);
+        size_t tb = h->sort_tmp_bytes;
+        if (n >= kOnesweepMin)          // large populations: onesweep (one pass per 8 key bits)
+            HIPCHK(h, rocprim::radix_sort_pairs<RaySortOnesweep>(h->w_sort_tmp.p, tb, kin, kout, vin, vout,
+                                                                 (size_t)n, b0, b1, h->stream));
+        else
+            HIPCHK(h, rocprim::radix_sort_pairs<RaySortCfg>(h->w_sort_tmp.p, tb, kin, kout, vin, vout, (size_t)n,
+                                                            b0, b1, h->stream));
+    }
+    out->perm = vout;
+    if (!L.ds && L.pt->npieces > 0 && L.pt->npieces <= 64 && L.pt->ngroups == 0) {
+        QueueArgs Qf;
+        QueueShape shf;
+        RETIF(queue_args(h, L, &Qf, &shf));
+        const dim3 gg((unsigned)((n + LPC_GR_T - 1) / LPC_GR_T));
+        with_bool(L.half, [&](auto hf) {
+            hipLaunchKernelGGL(k_gather_roots<decltype(hf)::value>, gg, dim3(LPC_GR_T), 0, h->stream,
+                               (const float4 *)h->w_aos.p, n, out->perm, (float *)h->w_rs.p, traced ? 1 : 0,
+                               (const Piece *)L.pt->pieces.p, (int)L.pt->npieces, Qf);
+        });
+        out->roots_done = true;
+    } else {
+        hipLaunchKernelGGL(k_gather_aos, dim3(grid1(n)), dim3(256), 0, h->stream, (const float4 *)h->w_aos.p, n,
+                           out->perm, (float *)h->w_rs.p, traced ? 1 : 0);
+    }
+    out->rs = (const float *)h->w_rs.p;
+    return 0;
+}
+
+// Where a launch's sliver tests run, and over which sliver pieces.
+//   merged (LPC_SLIVER_MERGE: from this population size, default every size):
+//     as units of the walk's own grid (k_rootwalk's tail), on the main stream;
+//   side: k_slivers beside the hierarchy stage on the side stream (both only add
+//     to the slots with order-independent atomics), launched after the hierarchy
+//     stage's kernels (the host reaches k_roots_s / k_rootwalk sooner), forked
+//     before the walk and joined after it.  One stream per trace keeps several
+//     traces in flight from interleaving fork / join events;
+//   neither: k_slivers before the walk on the main stream (no side stream).
+struct SliverPlan {
+    int32_t nsp = 0;                    // sliver pieces the rays can reach: dmin <= max |D| (sliver_dmin);
+    float dmax = 0.0f;                  //   device-sized: every piece in the grid, culled there by DevSize::dm2
+    bool merged = false, side = false;
+};
+static SliverPlan sliver_plan(lpc_handle *h, const Launch &L, double dmax2)
+{
+    SliverPlan S;
+    if (!(dmax2 >= 0.0)) dmax2 = INFINITY;      // NaN bound (a NaN direction): no culling
+    S.dmax = (float)std::min<double>(sqrt(dmax2 * (1.0 + 1e-5)), (double)INFINITY);
+    while (S.nsp < L.pt->nspieces && (L.ds || L.pt->sdmin[(size_t)S.nsp] <= S.dmax)) ++S.nsp;
+    S.merged = h->knobs.sliver_merge >= 0 && L.n >= h->knobs.sliver_merge && S.nsp > 0 && L.pt->npieces > 0;
+    S.side = !S.merged && S.nsp > 0 && side_stream(h);
+    return S;
+}
+
+// k_slivers' arguments (ppw packets per wave), or the merged units' (run_queue)
+static SliverArgs sliver_args(lpc_handle *h, const Launch &L, const SliverPlan &S, int64_t ppw)
+{
+    SliverArgs A;
+    memset(&A, 0, sizeof(A));
+    A.R = L.in; A.rs = L.rs; A.n = L.n; A.perm = L.perm; A.pk = (const PacketRec *)h->w_pk.p;
+    A.srec = (const SliverRec *)h->scene.d_srec.p; A.pieces = (const Piece *)L.pt->spieces.p; A.nsp = S.nsp;
+    A.ppw = (int)ppw; A.eps = L.eps; A.max_ray_len = L.max_ray_len; A.dmax = S.dmax;
+    A.skey = L.skey; A.scnt = L.scnt; A.stats = L.stats; A.nd = L.nd(); A.dm2d = L.ds ? L.ds->dm2 : nullptr;
+    A.tmask = L.tmask;
+    return A;
+}
+
+// The unmerged sliver tests: the packet bounds and k_slivers, on the side stream
+// between its fork and join events, or on the main stream.
+static int launch_slivers(lpc_handle *h, const Launch &L, const SliverPlan &S)
+{
+    const hipStream_t ss = S.side ? h->stream2 : h->stream;
+    if (S.side) HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_side[0], 0));
+    if (S.nsp > 0) {
+        // packets per wave: enough (packet, piece) waves to fill the GPU, no more
+        const int64_t npkx = (L.n + 127) / 128;
+        const int64_t ppw = std::max<int64_t>(1, npkx * S.nsp / kSliverWaves);
+        const dim3 sg((unsigned)((npkx + 4 * ppw - 1) / (4 * ppw)), (unsigned)S.nsp);
+        hipLaunchKernelGGL(k_packet<2>, dim3((unsigned)((npkx + 3) / 4)), dim3(256), 0, ss, L.in, L.rs, L.n,
+                           (PacketRec *)h->w_pk.p, L.nd());
+        hipLaunchKernelGGL(k_slivers, sg, dim3(256), 0, ss, sliver_args(h, L, S, ppw));
+        HIPCHK(h, hipGetLastError());
+    }
+    if (S.side) HIPCHK(h, hipEventRecord(h->ev_side[1], h->stream2));
+    return 0;
+}
 
 // intersect for a.n rays of a.rays into the slot arrays, and optionally into a
 // caller's [ray][mesh] buffers (st_user != NULL, the reference's scratch layout).
@@ -1075,219 +1287,49 @@ struct IsectOut {
 // launch shapes follow ds->pred.
 static int run_intersect(lpc_handle *h, const IsectIn &a, IsectOut *out)
 {
-    const RaysIn &in = a.rays;
-    int64_t n = a.n;
-    const float max_ray_len = a.max_ray_len;
-    const DevSize *ds = a.ds;
-    const bool traced = a.traced;
     *out = IsectOut();
-    RETIF(ensure_ws(h, n));
-    const int64_t nb = n;                          // capacity
-    if (ds) n = std::max<int64_t>(1, std::min(ds->pred, nb));   // launch shapes
-    if ((nb + 63) / 64 > (int64_t)LPC_Q_MAX_PACKETS)
+    RETIF(ensure_ws(h, a.n));
+    if ((a.n + 63) / 64 > (int64_t)LPC_Q_MAX_PACKETS)
         return set_err(h, LPC_E_STATE, "internal: chunk above the root items' packet bound");
-    // the pieces of the root items: q_level's cut (the same sliver pieces at every
-    // cut), coarser while k_roots_s cannot hold them (tiny populations)
-    PieceTable *pt;
-    int32_t g = q_level(h, n, traced && h->pop.traced);
-    RETIF(piece_table(h, &pt, g));
-    // (a table of more than 1 024 run roots, g = 1, goes to k_roots_s in batches)
-    while (pt->npieces > LPC_ROOTS_BATCH && g > 1) {
-        g = std::max(1, g / 8);
-        RETIF(piece_table(h, &pt, g));
-    }
-    const float eps = 0.000001f * max_ray_len;   // .cl:245, single-precision constant
-    unsigned long long *skey = (unsigned long long *)h->w_key.p;
-    int32_t *scnt = (int32_t *)h->w_sc.p;
-    uint32_t *misc = (uint32_t *)h->d_misc.p;
-    SlotInit SI;
-    SI.K = h->scene.K; SI.live = (const int32_t *)h->scene.d_live.p; SI.max_ray_len = max_ray_len;
-    SI.skey = skey; SI.scnt = scnt; SI.misc = misc;
-    SI.acc = h->acc_pending ? (DevAcc *)h->d_acc.p : nullptr;
-    SI.m_total = (unsigned long long)h->acc_pending_total;
-    SI.uniform = 0;
-    SI.tmask = nullptr;
-    h->acc_pending = false;
-    // traced mode: the children come out in their parents' traced order and need
-    // no sort of their own
-    const bool chained_pop = traced && h->pop.traced;
-    // a chained population keeps its parents' order, except a large one
-    // (LPC_RESORT_MIN): after many generations that order has lost its coherence
-    const bool sorted = n >= kSortMin && (!chained_pop || (!ds && n >= h->knobs.resort_min));
-    // the slot reset rides on k_raykey when it runs before everything that reads misc
-    const bool fold_init = sorted && n >= LPC_MISC_WORDS;
-    // Traced iterations (k_shade_stage) leave every slot they read in the clean
-    // state (max_ray_len, idx -1, count 0), so once the whole slot array is clean
-    // no slot needs a reset; only the launch words do (k_stage_move reset them for
-    // the next launch; the emitted rays' k_raykey does).
+    const bool chained = a.traced && h->pop.traced;   // children in their parents' traced order: no sort of their own
+    Launch L;
+    L.in = a.rays; L.ds = a.ds;
+    L.n = a.ds ? std::max<int64_t>(1, std::min(a.ds->pred, a.n)) : a.n;    // launch shapes
+    L.max_ray_len = a.max_ray_len; L.eps = 0.000001f * a.max_ray_len;       // .cl:245, single-precision constant
+    L.skey = (unsigned long long *)h->w_key.p; L.scnt = (int32_t *)h->w_sc.p;
+    L.stats = h->prof.stats ? (unsigned long long *)h->prof.d_stats.p : nullptr;
+    // written-slot masks: kept by every flush of this launch, read by its
+    // k_shade_stage (traced launches only; a mask bit may be stale, never missing:
+    // the masks are cleared with the slots, and only the traced path reads them)
+    L.tmask = out->tmask = (a.traced && h->scene.K <= 32) ? (uint32_t *)h->w_tm.p : nullptr;
     // LPC_HALF 3 (default): the half-line cull at the piece roots (k_roots_s items)
     // of a trace's chained populations; "emitted" = the trace's first population,
     // whatever the export mode; the drop-in kernels (lpc_intersect,
     // lpc_bounce_host: no trace population) are never culled.  0: off.
-    const bool half = a.trace && h->knobs.half == 3 && !h->pop.emitted;
-    const bool restore = traced;
-    const bool clean = restore && h->slots_clean && h->slots_mrl == max_ray_len;
-    // written-slot masks: kept by every flush of this launch, read by its
-    // k_shade_stage (restore path only; a mask bit may be stale, never missing:
-    // the masks are cleared with the slots, and only the restore path reads them)
-    uint32_t *const tmask = (restore && h->scene.K <= 32) ? (uint32_t *)h->w_tm.p : nullptr;
-    out->tmask = tmask;
-    const bool misc_clean = restore && h->misc_clean;
-    h->slots_clean = h->misc_clean = false;
-    SlotInit SIk = SI;
-    SIk.skey = nullptr; SIk.misc = nullptr; SIk.acc = nullptr;
-    if (restore && !clean) {            // the whole array to the clean state (stride-independent)
-        SI.uniform = 1;
-        SI.tmask = (uint32_t *)h->w_tm.p;
-        const int64_t all = h->ws_rays;
-        hipLaunchKernelGGL(k_slot_init, dim3(grid1(std::max<int64_t>(all, LPC_MISC_WORDS))), dim3(256), 0,
-                           h->stream, all, SI);
-    } else if (restore) {               // slots clean: the launch words only (k_stage_move writes all counters)
-        SI.skey = nullptr;
-        SI.acc = nullptr;
-        if (fold_init) SIk = SI;
-        else if (!misc_clean)
-            hipLaunchKernelGGL(k_slot_init, dim3(grid1(LPC_MISC_WORDS)), dim3(256), 0, h->stream, (int64_t)0, SI);
-    } else if (fold_init) {
-        SIk = SI;
-    } else {
-        hipLaunchKernelGGL(k_slot_init, dim3(grid1(std::max<int64_t>(n, LPC_MISC_WORDS))), dim3(256), 0, h->stream,
-                           n, SI);
+    L.half = a.trace && h->knobs.half == 3 && !h->pop.emitted;
+    RETIF(piece_cut(h, L.n, chained, &L.pt));
+    // a chained population keeps its parents' order, except a large one
+    // (LPC_RESORT_MIN): after many generations that order has lost its coherence
+    const bool sorted = L.n >= kSortMin && (!chained || (!a.ds && L.n >= h->knobs.resort_min));
+    const SlotState was = h->slots;
+    h->slots = SlotState();
+    const SlotInit SIk = slot_reset(h, L, a, /*fold*/ sorted && L.n >= LPC_MISC_WORDS, was);
+    Order ord;
+    if (sorted) RETIF(coherence_order(h, L, a, SIk, &ord));
+    L.rs = ord.rs;
+    L.perm = ord.perm;
+    if (a.traced) {                     // positions of the coherence order are the rays' indices from here on
+        out->traced = L.rs ? soa_rows<RaysIn>(L.rs, L.n) : L.in;
+        L.perm = nullptr;
     }
-    const int32_t *perm = nullptr;
-    const float *rs = nullptr;
-    bool roots_done = false;                    // k_gather_roots wrote the root items
-    const float *blo = h->scene.box_lo, *bsc = h->scene.box_scale;     // the coherence key's box
-    if (sorted) {
-        // coherence order: rays of one wave share origin cell and direction
-        // (key [scene-box origin cell | direction], k_raykey), gathered from the
-        // 32-byte rows k_raykey wrote
-        const size_t C = (size_t)h->ws_rays;
-        uint32_t *kin = (uint32_t *)h->w_sort.p, *kout = kin + C;
-        int32_t *vin = (int32_t *)(kout + C), *vout = vin + C;
-        // the emitted rays' varying key bits (set_rays)
-        int b0 = 0, b1 = 32;
-        if (traced && h->pop.emitted) { b0 = h->emitted.init_key_lo; b1 = h->emitted.init_key_hi; }
-        const int nbits = b1 - b0;
-        if (traced && h->pop.emitted && h->emitted.init_bsort && h->knobs.bsort && nbits >= 1 && nbits <= 16 &&
-            n >= LPC_MISC_WORDS) {
-            // counting sort (MSD, two 8-bit digits, stable), then the gather
-            const int hb = std::min(nbits, LPC_BS_HB), lb = nbits - hb;
-            const int64_t nblk = (n + LPC_BS_RPB - 1) / LPC_BS_RPB;
-            uint32_t *hist = (uint32_t *)h->w_bhist.p, *tot = hist + (size_t)LPC_BS_ND * nblk;
-            uint32_t *bst = tot + LPC_BS_ND;
-            hipLaunchKernelGGL(k_bkey, dim3((unsigned)nblk), dim3(LPC_BS_T), 0, h->stream, in, n, blo[0], blo[1],
-                               blo[2], bsc[0], bsc[1], bsc[2], kin, (float4 *)h->w_aos.p, SIk, b0, lb, hb, hist, nblk);
-            hipLaunchKernelGGL(k_bprefix, dim3(1u << hb), dim3(256), 0, h->stream, hist, nblk, tot);
-            hipLaunchKernelGGL(k_bscatter, dim3((unsigned)nblk), dim3(LPC_BS_T), 0, h->stream, (const uint32_t *)kin,
-                               n, b0, lb, hb, (const uint32_t *)hist, nblk, (const uint32_t *)tot, bst,
-                               (uint8_t *)kout, vin, vout);
-            if (lb > 0)
-                hipLaunchKernelGGL(k_bsort2, dim3(1u << hb, LPC_BS_MAXB / LPC_BS_RPB), dim3(LPC_BS_T), 0, h->stream,
-                                   (const uint8_t *)kout, (const int32_t *)vin, lb, (const uint32_t *)bst, vout);
-        } else {
-            // a re-sorted chained population: the key (5-D Morton) spans its own box
-            // (k_stage_move of the iteration that made it), not the scene's
-            const uint32_t *pbox = (traced && chained_pop && h->pop.pbox_ok) ? (const uint32_t *)h->d_pbox.p : nullptr;
-            hipLaunchKernelGGL(k_raykey, dim3(grid1(n)), dim3(256), 0, h->stream, in, n, blo[0], blo[1], blo[2], bsc[0],
-                               bsc[1], bsc[2], kin, vin, (float4 *)h->w_aos.p, SIk, pbox, pbox ? kKeyObits : 5,
-                               pbox ? 1 : 0);
-            size_t tb = h->sort_tmp_bytes;
-            if (n >= kOnesweepMin)          // large populations: onesweep (one pass per 8 key bits)
-                HIPCHK(h, rocprim::radix_sort_pairs<RaySortOnesweep>(h->w_sort_tmp.p, tb, kin, kout, vin, vout,
-                                                                     (size_t)n, b0, b1, h->stream));
-            else
-                HIPCHK(h, rocprim::radix_sort_pairs<RaySortCfg>(h->w_sort_tmp.p, tb, kin, kout, vin, vout, (size_t)n,
-                                                                b0, b1, h->stream));
-        }
-        perm = vout;
-        // the gather with the root tests fused in (k_gather_roots), when the
-        // launch has one root-test task per packet and no run gate
-        if (!ds && pt->npieces > 0 && pt->npieces <= 64 && pt->ngroups == 0) {
-            QueueArgs Qf;
-            QueueShape shf;
-            RETIF(queue_args(h, n, pt, nullptr, &Qf, &shf));
-            const dim3 gg((unsigned)((n + LPC_GR_T - 1) / LPC_GR_T));
-            with_bool(half, [&](auto hf) {
-                hipLaunchKernelGGL(k_gather_roots<decltype(hf)::value>, gg, dim3(LPC_GR_T), 0, h->stream,
-                                   (const float4 *)h->w_aos.p, n, perm, (float *)h->w_rs.p, traced ? 1 : 0,
-                                   (const Piece *)pt->pieces.p, (int)pt->npieces, Qf);
-            });
-            roots_done = true;
-        } else {
-            hipLaunchKernelGGL(k_gather_aos, dim3(grid1(n)), dim3(256), 0, h->stream, (const float4 *)h->w_aos.p, n,
-                               perm, (float *)h->w_rs.p, traced ? 1 : 0);
-        }
-        rs = (const float *)h->w_rs.p;
-    }
-    if (traced) {
-        // positions of the coherence order are the rays' indices from here on
-        if (rs) {
-            const float *f = rs;
-            RaysIn t;
-            t.ox = f; t.oy = f + n; t.oz = f + 2 * n; t.dx = f + 3 * n; t.dy = f + 4 * n; t.dz = f + 5 * n;
-            t.pw = f + 6 * n; t.pmid = (const int32_t *)(f + 7 * n);
-            out->traced = t;
-        } else {
-            out->traced = in;
-        }
-        perm = nullptr;
-    }
-    unsigned long long *stats = h->prof.stats ? (unsigned long long *)h->prof.d_stats.p : nullptr;
-    // sliver pieces the launch's rays can reach: dmin <= max |D| (sliver_dmin)
-    const double dmax2 = a.dmax2 >= 0.0 ? a.dmax2 : INFINITY;   // NaN bound (a NaN direction): no culling
-    const float dmax = (float)std::min<double>(sqrt(dmax2 * (1.0 + 1e-5)), (double)INFINITY);
-    int32_t nsp = 0;
-    while (nsp < pt->nspieces && (ds || pt->sdmin[(size_t)nsp] <= dmax)) ++nsp;
-    // device-sized: the population's max |D| read on the device (every sliver piece
-    // in the grid, culled there)
-    const unsigned *dm2_dev = ds ? ds->dm2 : nullptr;
-    const long long *nd_dev = ds ? ds->nd : nullptr;
-    // LPC_SLIVER_MERGE: from this population size (default 0: every size) the
-    // sliver units run in the walk's own grid (k_rootwalk's tail) on this stream;
-    // below, k_slivers runs beside the hierarchy stage on a second stream (both
-    // only add to the slots with order-independent atomics; joined at the end),
-    // launched after the hierarchy stage's kernels (the host reaches k_roots_s /
-    // k_rootwalk sooner).  One stream per trace keeps several traces in flight
-    // from interleaving fork / join events
-    const bool merge_try = h->knobs.sliver_merge >= 0 && n >= h->knobs.sliver_merge && nsp > 0 && pt->npieces > 0;
-    const bool side = !merge_try && nsp > 0 && side_stream(h);
-    hipStream_t ss = h->stream;
-    if (side) {
-        ss = h->stream2;
-        HIPCHK(h, hipEventRecord(h->ev_side[0], h->stream));
-    }
-    auto sliver_args = [&](int64_t ppw) {
-        SliverArgs A;
-        memset(&A, 0, sizeof(A));
-        A.R = in; A.rs = rs; A.n = n; A.perm = perm; A.pk = (const PacketRec *)h->w_pk.p;
-        A.srec = (const SliverRec *)h->scene.d_srec.p; A.pieces = (const Piece *)pt->spieces.p; A.nsp = nsp;
-        A.ppw = (int)ppw; A.eps = eps; A.max_ray_len = max_ray_len; A.dmax = dmax;
-        A.skey = skey; A.scnt = scnt; A.stats = stats; A.nd = nd_dev; A.dm2d = dm2_dev; A.tmask = tmask;
-        return A;
-    };
-    auto launch_slivers = [&]() -> int {
-        if (side) HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_side[0], 0));
-        if (nsp > 0) {
-            // packets per wave: enough (packet, piece) waves to fill the GPU, no more
-            const int64_t npkx = (n + 127) / 128;
-            const int64_t ppw = std::max<int64_t>(1, npkx * nsp / kSliverWaves);
-            const dim3 sg((unsigned)((npkx + 4 * ppw - 1) / (4 * ppw)), (unsigned)nsp);
-            hipLaunchKernelGGL(k_packet<2>, dim3((unsigned)((npkx + 3) / 4)), dim3(256), 0, ss, in, rs, n,
-                               (PacketRec *)h->w_pk.p, nd_dev);
-            hipLaunchKernelGGL(k_slivers, sg, dim3(256), 0, ss, sliver_args(ppw));
-            HIPCHK(h, hipGetLastError());
-        }
-        if (side) HIPCHK(h, hipEventRecord(h->ev_side[1], h->stream2));
-        return 0;
-    };
-    if (!side && !merge_try) RETIF(launch_slivers());       // no side stream: before the walk, this stream
+    const SliverPlan S = sliver_plan(h, L, a.dmax2);
+    if (S.side) HIPCHK(h, hipEventRecord(h->ev_side[0], h->stream));     // fork
+    if (!S.side && !S.merged) RETIF(launch_slivers(h, L, S));
     Event e0, e1;
     if (h->prof.on && !h->prof.light) { e0 = ev_get(h); e1 = ev_get(h); (void)hipEventRecord(e0, h->stream); }
-    if (pt->npieces > 0) {
-        const SliverArgs SAm = sliver_args(kSliverMergePpw);
-        RETIF(run_queue(h, in, rs, n, perm, pt, eps, max_ray_len, skey, scnt, stats, ds, merge_try ? &SAm : nullptr,
-                        roots_done, half, tmask, &out->sampled));
+    if (L.pt->npieces > 0) {
+        const SliverArgs SAm = sliver_args(h, L, S, kSliverMergePpw);
+        RETIF(run_queue(h, L, S.merged ? &SAm : nullptr, ord.roots_done, &out->sampled));
     }
     if (h->prof.on) {      // the intersect stage: the walk (+ k_packet, k_slivers)
         if (!h->prof.light) {
@@ -1296,15 +1338,17 @@ static int run_intersect(lpc_handle *h, const IsectIn &a, IsectOut *out)
         }
         if (!h->prof.light || out->sampled) {
             h->prof.launches += 1;
-            h->prof.pairs += n * (int64_t)h->scene.M;
+            h->prof.pairs += L.n * (int64_t)h->scene.M;
         }
     }
-    if (side) RETIF(launch_slivers());
-    if (side) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_side[1], 0));
+    if (S.side) {
+        RETIF(launch_slivers(h, L, S));
+        HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_side[1], 0));     // join
+    }
     if (a.st_user) {
-        hipLaunchKernelGGL(k_slot_export, dim3(grid1(n)), dim3(256), 0, h->stream, n, h->scene.K,
-                           (const int32_t *)h->scene.d_live.p, (const unsigned long long *)skey,
-                           (const int32_t *)scnt, a.st_user, a.si_user, a.sc_user, 1);
+        hipLaunchKernelGGL(k_slot_export, dim3(grid1(L.n)), dim3(256), 0, h->stream, L.n, h->scene.K,
+                           (const int32_t *)h->scene.d_live.p, (const unsigned long long *)L.skey,
+                           (const int32_t *)L.scnt, a.st_user, a.si_user, a.sc_user, 1);
     }
     HIPCHK(h, hipGetLastError());
     return 0;
@@ -1446,7 +1490,6 @@ int lpc_open(int device, lpc_handle **out)
     k.spill_large_per_tri = env_int("LPC_LARGE_PER_TRI", k.spill_large_per_tri);
     k.spill_cap = std::max<int64_t>(env_int("LPC_SPILL_CAP", k.spill_cap), 64);
     k.host_prof = (int)env_int("LPC_HOSTPROF", 0);
-    k.stage_mode = (int)std::min<int64_t>(2, std::max<int64_t>(0, env_int("LPC_STAGE_MODE", k.stage_mode)));
     k.map_slices = (int)std::min<int64_t>(1024, std::max<int64_t>(0, env_int("LPC_MAP_SLICES", k.map_slices)));
     k.map_per_cu = (int)std::min<int64_t>(64, std::max<int64_t>(1, env_int("LPC_MAP_PER_CU", k.map_per_cu)));
     if (h->acc_map.alloc(kAccRing * sizeof(DevAcc), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
@@ -1711,6 +1754,15 @@ static double host_dmax2(int64_t n, const float *dir4)
     return m;
 }
 
+// (n,4) origin and direction rows on the device into the six SoA arrays that
+// start at dst, `st` floats apart (a population: Pop::f(0) + first row, its
+// capacity), on stream s.
+static void unpack_rays(hipStream_t s, int64_t n, const float4 *o4, const float4 *d4, float *dst, size_t st)
+{
+    hipLaunchKernelGGL(k_unpack4, dim3(grid1(n)), dim3(256), 0, s, n, o4, dst, dst + st, dst + 2 * st);
+    hipLaunchKernelGGL(k_unpack4, dim3(grid1(n)), dim3(256), 0, s, n, d4, dst + 3 * st, dst + 4 * st, dst + 5 * st);
+}
+
 // Upload (n,4) host rows into SoA arrays of a population (rows 0..n): both row
 // arrays into one staging buffer (the copies return once the host arrays are
 // read), then the unpacks on the stream; `sync`: wait for them (the caller may
@@ -1723,10 +1775,7 @@ static int upload_rays(lpc_handle *h, Pop &P, int64_t n, const float *origin4, c
     HIPCHK(h, hipMemcpy(so, origin4, (size_t)n * 16, hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(sd, dir4, (size_t)n * 16, hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(P.f(6), pow, (size_t)n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_unpack4, dim3(grid1(n)), dim3(256), 0, h->stream, n, (const float4 *)so, P.f(0), P.f(1),
-                       P.f(2));
-    hipLaunchKernelGGL(k_unpack4, dim3(grid1(n)), dim3(256), 0, h->stream, n, (const float4 *)sd, P.f(3), P.f(4),
-                       P.f(5));
+    unpack_rays(h->stream, n, so, sd, P.f(0), (size_t)P.cap);
     if (prev_mid) HIPCHK(h, hipMemcpy(P.pmid(), prev_mid, (size_t)n * 4, hipMemcpyHostToDevice));
     else                                        // just emitted (-2, iterative_tracer.py:118), filled on the device
         HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)P.pmid(), -2, (size_t)n, h->stream));
@@ -1818,13 +1867,9 @@ int lpc_intersect(lpc_handle *h, int64_t n, const float *dev_origin4, const floa
     const size_t Cw = (size_t)h->ws_rays;
     for (int64_t base = 0; base < n; base += C) {
         const int64_t nc = std::min(C, n - base);
-        hipLaunchKernelGGL(k_unpack4, dim3(grid1(nc)), dim3(256), 0, h->stream, nc,
-                           (const float4 *)dev_origin4 + base, s, s + Cw, s + 2 * Cw);
-        hipLaunchKernelGGL(k_unpack4, dim3(grid1(nc)), dim3(256), 0, h->stream, nc,
-                           (const float4 *)dev_dir4 + base, s + 3 * Cw, s + 4 * Cw, s + 5 * Cw);
-        RaysIn in;
-        in.ox = s; in.oy = s + Cw; in.oz = s + 2 * Cw; in.dx = s + 3 * Cw; in.dy = s + 4 * Cw;
-        in.dz = s + 5 * Cw; in.pw = nullptr; in.pmid = nullptr;
+        unpack_rays(h->stream, nc, (const float4 *)dev_origin4 + base, (const float4 *)dev_dir4 + base, s, Cw);
+        RaysIn in = soa_rows<RaysIn>((const float *)s, (int64_t)Cw);
+        in.pw = nullptr; in.pmid = nullptr;
         IsectOut io;
         const int64_t b = base * h->scene.K;
         RETIF(run_intersect(h, IsectIn{in, nc, max_ray_len, INFINITY, dev_tmin + b, dev_itmp + b, dev_cnt + b}, &io));
@@ -2023,14 +2068,13 @@ int lpc_trace_reset(lpc_handle *h)
 }
 
 // ---- streamed batches of new rays ------------------------------------------
-// A staged batch is copied by a helper thread: the caller's (n,4) rows
-// transposed into the slot's pinned staging as the population's SoA arrays (a
-// few host threads, chunk by chunk, each chunk's DMAs queued as soon as it is
-// ready: 28 B per ray cross PCIe), the emitted rays' fills and k_ray_scan, all on
-// the copy stream, which first
-// waits for the main-stream work queued when the batch was staged (the slot's
-// buffers may hold an earlier batch's emitted rays).  The main thread meanwhile
-// traces the batch before it.
+// A staged batch is copied by a helper thread: the caller's (n,4) rows as they
+// are (pageable DMA, 36 B per ray cross PCIe; staging them in pinned memory, as
+// rows or transposed, measured slower and was removed: DESIGN.md section 7f),
+// their unpack, the emitted rays' fills and k_ray_scan, all on the copy stream,
+// which first waits for the main-stream work queued when the batch was staged
+// (the slot's buffers may hold an earlier batch's emitted rays).  The main
+// thread meanwhile traces the batch before it.
 static void stage_worker(lpc_handle *h, lpc_handle::RaySlot *s, const float *origin4, const float *dir4,
                          const float *pow, std::array<float, 6> box, bool scan)   // box: the key box lo | scale
 {
@@ -2043,56 +2087,16 @@ static void stage_worker(lpc_handle *h, lpc_handle::RaySlot *s, const float *ori
     if (e != hipSuccess) { fail(e, "hipSetDevice"); return; }
     const int64_t n = s->n;
     hipStream_t cs = h->stage.cstream;
-    const int mode = h->knobs.stage_mode;
-    if (mode == 2) {
-        // chunks: the host transposes chunk c + 1 into the pinned SoA arrays while
-        // the DMAs of chunk c run (28 B per ray cross PCIe)
-        float *pin = (float *)s->pin.p;
-        const int64_t CH = (int64_t)1 << 18;
-        const int T = std::max(1, std::min(4, host_threads()));
-        for (int64_t lo = 0; lo < n; lo += CH) {
-            const int64_t hi = std::min(n, lo + CH);
-            host_parts(hi - lo, T, [&](int64_t a, int64_t b, int) {
-                for (int64_t i = lo + a; i < lo + b; ++i) {
-                    const float *o = origin4 + 4 * i, *d = dir4 + 4 * i;
-                    pin[i] = o[0]; pin[n + i] = o[1]; pin[2 * n + i] = o[2];
-                    pin[3 * n + i] = d[0]; pin[4 * n + i] = d[1]; pin[5 * n + i] = d[2];
-                }
-                memcpy(pin + 6 * n + lo + a, pow + lo + a, (size_t)(b - a) * 4);
-            });
-            for (int k = 0; k < 7; ++k)
-                if ((e = hipMemcpyAsync(s->P.f(k) + lo, pin + (size_t)k * n + lo, (size_t)(hi - lo) * 4,
-                                        hipMemcpyHostToDevice, cs)) != hipSuccess) {
-                    fail(e, "copy");
-                    return;
-                }
-        }
-    } else {
-        // the (n,4) rows as they are: from the caller's memory (mode 0: the
-        // runtime's own staging of a pageable copy) or through the slot's pinned
-        // block (mode 1: host threads copy, one DMA), unpacked on the device
-        float4 *so = (float4 *)s->aos.p, *sd = so + n;
-        const char *src_o = (const char *)origin4, *src_d = (const char *)dir4, *src_p = (const char *)pow;
-        if (mode == 1) {
-            char *pin = (char *)s->pin.p;
-            host_parts(n, host_threads(), [&](int64_t lo, int64_t hi, int) {
-                memcpy(pin + (size_t)lo * 16, origin4 + 4 * lo, (size_t)(hi - lo) * 16);
-                memcpy(pin + (size_t)n * 16 + (size_t)lo * 16, dir4 + 4 * lo, (size_t)(hi - lo) * 16);
-                memcpy(pin + (size_t)n * 32 + (size_t)lo * 4, pow + lo, (size_t)(hi - lo) * 4);
-            });
-            src_o = pin; src_d = pin + (size_t)n * 16; src_p = pin + (size_t)n * 32;
-        }
-        if ((e = hipMemcpyAsync(so, src_o, (size_t)n * 16, hipMemcpyHostToDevice, cs)) != hipSuccess ||
-            (e = hipMemcpyAsync(sd, src_d, (size_t)n * 16, hipMemcpyHostToDevice, cs)) != hipSuccess ||
-            (e = hipMemcpyAsync(s->P.f(6), src_p, (size_t)n * 4, hipMemcpyHostToDevice, cs)) != hipSuccess) {
-            fail(e, "copy");
-            return;
-        }
-        hipLaunchKernelGGL(k_unpack4, dim3(grid1(n)), dim3(256), 0, cs, n, (const float4 *)so, s->P.f(0), s->P.f(1),
-                           s->P.f(2));
-        hipLaunchKernelGGL(k_unpack4, dim3(grid1(n)), dim3(256), 0, cs, n, (const float4 *)sd, s->P.f(3), s->P.f(4),
-                           s->P.f(5));
+    // the (n,4) rows as they are, from the caller's memory (the runtime's own
+    // staging of a pageable copy), unpacked on the device
+    float4 *so = (float4 *)s->aos.p, *sd = so + n;
+    if ((e = hipMemcpyAsync(so, origin4, (size_t)n * 16, hipMemcpyHostToDevice, cs)) != hipSuccess ||
+        (e = hipMemcpyAsync(sd, dir4, (size_t)n * 16, hipMemcpyHostToDevice, cs)) != hipSuccess ||
+        (e = hipMemcpyAsync(s->P.f(6), pow, (size_t)n * 4, hipMemcpyHostToDevice, cs)) != hipSuccess) {
+        fail(e, "copy");
+        return;
     }
+    unpack_rays(cs, n, so, sd, s->P.f(0), (size_t)s->P.cap);
     if ((e = hipMemsetD32Async((hipDeviceptr_t)s->P.pmid(), -2, (size_t)n, cs)) != hipSuccess) { fail(e, "fill"); return; }
     if (scan) {                                     // the scene's key box is known: the analysis rides along
         if ((e = hipMemsetAsync(s->scan.p, 0, sizeof(RayScan), cs)) != hipSuccess) { fail(e, "fill"); return; }
@@ -2108,8 +2112,8 @@ static void stage_worker(lpc_handle *h, lpc_handle::RaySlot *s, const float *ori
     if (h->knobs.host_prof) {
         const double t1 = host_us();
         (void)hipEventSynchronize(s->ev);
-        fprintf(stderr, "[lpc host] stage mode %d: %lld rays, enqueued %.1f us, done %.1f us\n", mode, (long long)n,
-                t1 - t0, host_us() - t0);
+        fprintf(stderr, "[lpc host] stage: %lld rays, enqueued %.1f us, done %.1f us\n", (long long)n, t1 - t0,
+                host_us() - t0);
     }
 }
 
@@ -2131,12 +2135,7 @@ int lpc_trace_stage_rays(lpc_handle *h, int64_t n, const float *origin4, const f
     // buffers (allocations synchronise; they grow only with the batch size)
     RETIF(pop_reserve(h, s.P, n));
     RETIF(dalloc(h, s.scan, sizeof(RayScan)));
-    if (h->knobs.stage_mode != 2) RETIF(dalloc(h, s.aos, (size_t)n * 32));
-    const size_t pb = (size_t)n * (h->knobs.stage_mode == 2 ? 28 : 36);
-    if (h->knobs.stage_mode != 0 && s.pin.bytes < pb) {
-        if (s.pin) (void)hipStreamSynchronize(h->stage.cstream);    // its last copies end before it goes
-        HIPCHK(h, s.pin.alloc(pb));
-    }
+    RETIF(dalloc(h, s.aos, (size_t)n * 32));
     s.n = n;
     s.max_ray_len = max_ray_len;
     s.ior_env = ior_env;
@@ -2443,7 +2442,7 @@ struct Pending {
     bool ds = false;            // device-sized (speculative)
     bool empty = false;         // nothing to do (n_in 0, host-sized)
     int64_t n_bound = 0;        // device-sized: population bound
-    double thr = -INFINITY;     // fused: the stop threshold its k_stage_move applied (ds_thr)
+    double thr = -INFINITY;     // fused: the stop threshold its k_stage_move applied (IterPlan::thr)
     bool bud = false;           // it ran with the power budget on: its per-mesh staging table ...
     int bpar = 0;               // ... of this parity joins the trace's when it is collected
     PopState before;            // the population's role before its enqueue (undo of a discarded speculative iteration)
@@ -2540,6 +2539,12 @@ struct IterOut {
 struct IterPlan {
     int64_t N = 0, C = 0;                   // the population (device-sized: its bound), rays per chunk
     const DevSize *ds = nullptr;
+    const long long *nd() const { return ds ? ds->nd : nullptr; }
+    // fused: the stop threshold k_stage_move writes into the next IterCtl entry.
+    // Only a device-sized iteration reads an entry, and only the one written by
+    // the iteration enqueued immediately before it, which is trace_run's own:
+    // what the other callers pass (-INFINITY) reaches no launch.
+    double thr = -INFINITY;
     DevAcc *host_acc = nullptr;             // early: the mapped ring slot the counters are published to
     unsigned seq = 0;
     bool want_box = false;                  // fused: the chunks write the children's origin box (d_pbox)
@@ -2676,7 +2681,7 @@ static int enqueue_fused_chunk(lpc_handle *h, const IterPlan &I, const RaysIn &i
     const int64_t nt_max = (nc + LPC_ST_TILE - 1) / LPC_ST_TILE;     // tiles the launch may touch
     StageArgs G;
     G.S = shade_args(h, in, nullptr, nc, h->emitted.max_ray_len, h->emitted.ior_env, false);
-    G.nd = ds ? ds->nd : nullptr;
+    G.nd = I.nd();
     G.stR = (float *)h->w_shf.p; G.stT = (float *)h->w_shi.p;   // the 20 shade-output arrays hold the staging rows
     G.stM = (float *)h->w_soa.p; G.cst = (int64_t)Cs;
     G.tpow = (double *)h->w_fc.p; G.tcnt = (uint32_t *)(G.tpow + ntc); G.tdm = G.tcnt + ntc;
@@ -2687,7 +2692,8 @@ static int enqueue_fused_chunk(lpc_handle *h, const IterPlan &I, const RaysIn &i
     G.tmp = (double *)(G.tdm + ntc);            // 16 ntc bytes in: 8-aligned
     const int64_t ng = (nt_max + LPC_ST_GROUP - 1) / LPC_ST_GROUP;
     unsigned long long *gs = (unsigned long long *)h->w_gsum.p;
-    G.gsum = gs + (size_t)h->gpar * (size_t)h->gcap;
+    const GroupWords::Turn gt = h->groups.turn(ng);     // this launch's k_shade_stage adds into its first ng groups
+    G.gsum = gs + gt.cur;
     G.tmask = tmask;
     G.tbox = I.want_box ? (uint32_t *)h->w_tbox.p : nullptr;
     G.cut = h->min_power; G.tcc = (uint32_t *)I.CS.cc; G.tcp = (double *)I.CS.cp;
@@ -2716,10 +2722,10 @@ static int enqueue_fused_chunk(lpc_handle *h, const IterPlan &I, const RaysIn &i
     M.acc = (DevAcc *)h->d_acc.p; M.host_acc = I.host_acc; M.seq = I.seq;
     M.misc = (uint32_t *)h->d_misc.p;
     M.mrun = (double *)h->d_mrun.p;
-    M.gsum_next = gs + (size_t)(1 - h->gpar) * (size_t)h->gcap;
-    M.gdirty_next = h->gdirty[1 - h->gpar];
+    M.gsum_next = gs + gt.next;
+    M.gdirty_next = gt.dirty_next;
     M.ctl = (IterCtl *)h->d_ctl.p; M.par = h->ctl_par;
-    M.thr = h->ds_thr; M.nmax = ds_cap(h); M.dcap2 = h->scene.dcap * h->scene.dcap * (1.0 - 1e-6);
+    M.thr = I.thr; M.nmax = ds_cap(h); M.dcap2 = h->scene.dcap * h->scene.dcap * (1.0 - 1e-6);
     M.tbox = G.tbox; M.pbox = G.tbox ? (uint32_t *)h->d_pbox.p : nullptr;
     M.popT = nullptr; M.capT = 0; M.cbase_in = nullptr; M.cbase_out = nullptr;
     M.first = 1; M.last = 1;
@@ -2732,17 +2738,13 @@ static int enqueue_fused_chunk(lpc_handle *h, const IterPlan &I, const RaysIn &i
         M.last = base + nc >= I.N ? 1 : 0;
         if (!M.last) { M.host_acc = nullptr; M.ctl = nullptr; }   // the last chunk publishes the totals
     }
-    h->gdirty[1 - h->gpar] = 0;
-    h->gdirty[h->gpar] = ng;            // this launch's k_shade_stage adds into its first ng groups
-    h->gpar = 1 - h->gpar;
     with_bool(ds != nullptr, [&](auto dsz) {
         hipLaunchKernelGGL(k_stage_move<decltype(dsz)::value>, dim3((unsigned)nt), dim3(LPC_ST_TILE), 0, h->stream, M);
     });
-    if (I.cut) cull_sum(h, I, base, nt_max, LPC_ST_TILE, ds ? ds->nd : nullptr);
-    if (I.bud) budget_sum(h, I, nc, ds ? ds->nd : nullptr);
-    h->slots_clean = true;              // k_shade_stage restored what it read
-    h->slots_mrl = h->emitted.max_ray_len;
-    h->misc_clean = true;               // k_stage_move reset the next launch's words
+    if (I.cut) cull_sum(h, I, base, nt_max, LPC_ST_TILE, I.nd());
+    if (I.bud) budget_sum(h, I, nc, I.nd());
+    // k_shade_stage restored what it read, k_stage_move reset the next launch's words
+    h->slots = SlotState{/*clean*/ true, h->emitted.max_ray_len, /*misc_clean*/ true};
     HIPCHK(h, hipGetLastError());
     return 0;
 }
@@ -2818,7 +2820,9 @@ static int enqueue_plain_chunk(lpc_handle *h, const IterPlan &I, const IterOut &
 // Enqueue one iteration over the current population (host-sized: h->pop.n rays;
 // ds != NULL: device-sized, traced single-chunk only).  Host bookkeeping that
 // needs no counters (the population's role) happens here; iter_collect the rest.
-static int iter_enqueue(lpc_handle *h, const IterOut &O, const DevSize *ds, Pending *P)
+// thr: the stop threshold a fused iteration's k_stage_move applies when it sizes
+// the iteration after it (IterPlan::thr).
+static int iter_enqueue(lpc_handle *h, const IterOut &O, const DevSize *ds, double thr, Pending *P)
 {
     *P = Pending();
     P->before = h->pop;
@@ -2844,15 +2848,14 @@ static int iter_enqueue(lpc_handle *h, const IterOut &O, const DevSize *ds, Pend
         fprintf(stderr, "[lpc host]   buffers %.1f us (m_total %lld inflight %lld m_cap %lld)\n", host_us() - hp0,
                 (long long)h->m_total, (long long)h->m_inflight, (long long)h->m_cap);
     h->m_inflight += N;
-    if (ds) {
-        h->acc_pending = false;         // k_stage_move writes every counter
-    } else if (C >= N) {                // one chunk: the counters reset rides on the slot reset
-        h->acc_pending = true;
-        h->acc_pending_total = h->m_total;
-    } else {
+    IsectIn ii;
+    // the counters' reset: device-sized, none (k_stage_move writes every counter);
+    // one chunk, it rides on that chunk's slot reset; several, a launch of its own
+    ii.acc_reset = !ds && C >= N;
+    ii.acc_total = h->m_total;
+    if (!ds && C < N)
         hipLaunchKernelGGL(k_acc_init, dim3(1), dim3(64), 0, h->stream, (DevAcc *)h->d_acc.p,
                            (unsigned long long)h->m_total);
-    }
     // traced mode: no per-ray export (the population then comes out in its
     // parents' coherence order; measured rays per iteration likewise), shaded and
     // compacted fused (enqueue_fused_chunk)
@@ -2867,13 +2870,12 @@ static int iter_enqueue(lpc_handle *h, const IterOut &O, const DevSize *ds, Pend
     if (traced && C < N) RETIF(dalloc(h, h->d_cbase, 8 * sizeof(unsigned long long)));
     if (ds && !(traced && early)) return set_err(h, LPC_E_STATE, "internal: device-sized iteration off the fused path");
     P->fused = traced;
-    P->thr = h->ds_thr;
+    P->thr = I.thr = thr;
     // fused: it sums the measured power per measure mesh when they fit (StageArgs::nmp)
     P->mp_fused = traced && h->scene.meas_meshes.size() <= (size_t)LPC_MP_MAX;
     I.host_acc = early ? h->acc_map_dev + P->seq % kAccRing : nullptr;
     // fused: the children's origin box when they may be re-sorted (population >= LPC_RESORT_MIN)
     I.want_box = traced && !ds && 2 * N >= h->knobs.resort_min;
-    IsectIn ii;
     ii.max_ray_len = h->emitted.max_ray_len; ii.dmax2 = h->pop.dmax2; ii.ds = ds;
     ii.trace = true; ii.traced = traced;
     const bool timed = h->prof.on && !h->prof.light;
@@ -2992,7 +2994,7 @@ int lpc_trace_iterate(lpc_handle *h, float *out_origin4, float *out_dest4, float
     RETIF(need_rays(h, "trace_iterate"));
     HIPCHK(h, hipSetDevice(h->device));
     Pending P;
-    RETIF(iter_enqueue(h, IterOut{out_origin4, out_dest4, out_pow, out_meas, out_next_pow}, nullptr, &P));
+    RETIF(iter_enqueue(h, IterOut{out_origin4, out_dest4, out_pow, out_meas, out_next_pow}, nullptr, -INFINITY, &P));
     if (h->knobs.host_prof && !P.empty)
         fprintf(stderr, "[lpc host] n %lld  launch %.1f us\n", (long long)P.n_in, host_us() - t_enter);
     return iter_collect(h, P, out_next_pow, st);
@@ -3009,7 +3011,7 @@ int lpc_trace_iterate_export(lpc_handle *h, void *host, int32_t flags, lpc_iter_
     IterOut O;
     O.X = &X;
     Pending P;
-    RETIF(iter_enqueue(h, O, nullptr, &P));
+    RETIF(iter_enqueue(h, O, nullptr, -INFINITY, &P));
     if (h->knobs.host_prof && !P.empty)
         fprintf(stderr, "[lpc host] n %lld  export launch %.1f us\n", (long long)P.n_in, host_us() - t_enter);
     return iter_collect(h, P, nullptr, st);
@@ -3093,11 +3095,10 @@ static int trace_run(lpc_handle *h, int32_t max_iter, double power_threshold, lp
     const bool hist_ok = n0 > 0 && h->hist_iter == max_iter && !h->hist_r.empty();
     h->dcap_rebuilt = false;
     std::vector<int64_t> seen;
-    // the device's stop rule for speculative iterations (k_stage_move): the
-    // threshold on this device's own power left -- or, in a sharded trace, none:
-    // the power left is a sum over all ranks, only the host sees it after the
-    // exchange, and a speculative iteration the ranks' sums end is dropped
-    h->ds_thr = h->xchg ? -INFINITY : power_threshold;
+    // the device's stop rule for speculative iterations (k_stage_move, local_thr
+    // below): the threshold on this device's own power left -- or, in a sharded
+    // trace, none: the power left is a sum over all ranks, only the host sees it
+    // after the exchange, and a speculative iteration the ranks' sums end is dropped;
     // sharded: a conservative local rule.  The device may stop the trace only when
     // the ranks' sum is certain to fall below the threshold: with passive
     // materials and non-negative powers a population's power never grows, so the
@@ -3120,8 +3121,7 @@ static int trace_run(lpc_handle *h, int32_t max_iter, double power_threshold, lp
     bool have_cur = false, have_nxt = false;
     for (int32_t i = 0; i < max_iter; ++i) {
         if (!have_cur) {
-            h->ds_thr = local_thr(i);
-            if ((rc = iter_enqueue(h, IterOut(), nullptr, &cur))) break;
+            if ((rc = iter_enqueue(h, IterOut(), nullptr, local_thr(i), &cur))) break;
             have_cur = true;
         }
         // iteration i + 1, device-sized, while iteration i runs (its population is
@@ -3139,8 +3139,7 @@ static int trace_run(lpc_handle *h, int32_t max_iter, double power_threshold, lp
                 D.dm2 = &ctl->dm2[h->ctl_par];
                 D.pred = std::max<int64_t>(1, std::min(pred_n, bound));
                 D.bound = bound;
-                h->ds_thr = local_thr(i + 1);
-                if ((rc = iter_enqueue(h, IterOut(), &D, &nxt))) break;
+                if ((rc = iter_enqueue(h, IterOut(), &D, local_thr(i + 1), &nxt))) break;
                 have_nxt = true;
             }
         }
@@ -3962,10 +3961,8 @@ int lpc_trace_set_rays_dev(lpc_handle *h, lpc_rays *const *list, int32_t count, 
             const lpc_rays *r = list[k];
             if (r->n == 0) continue;
             HIPCHK(h, hipStreamWaitEvent(h->stream, r->ready, 0));
-            hipLaunchKernelGGL(k_unpack4, dim3(grid1(r->n)), dim3(256), 0, h->stream, r->n, (const float4 *)r->origin(),
-                               h->I.f(0) + off, h->I.f(1) + off, h->I.f(2) + off);
-            hipLaunchKernelGGL(k_unpack4, dim3(grid1(r->n)), dim3(256), 0, h->stream, r->n, (const float4 *)r->dir(),
-                               h->I.f(3) + off, h->I.f(4) + off, h->I.f(5) + off);
+            unpack_rays(h->stream, r->n, (const float4 *)r->origin(), (const float4 *)r->dir(), h->I.f(0) + off,
+                        (size_t)h->I.cap);
             HIPCHK(h, hipMemcpyAsync(h->I.f(6) + off, r->pow(), (size_t)r->n * 4, hipMemcpyDeviceToDevice, h->stream));
             off += r->n;
         }

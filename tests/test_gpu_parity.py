@@ -399,6 +399,58 @@ def test_clean_slots_across_paths(oracle_mod):
         np.testing.assert_array_equal(got[2], want[2])
 
 
+def _lens_regrow():
+    small, large = (scenes.lens(n=n, seed=31) for n in (300, 4160))
+    thr = (1.0 - large.tau) * float(np.sum(rays_of(large)[2], dtype=np.float64))
+    return (lambda e: e.upload_meshes(large.meshes), rays_of(small), rays_of(large), large.max_ray_len, large.ior_env,
+            large.iterations, thr)
+
+
+def _fates_regrow():
+    import fate_util as fu
+    sc = fu.layout(1, 33)                               # more than 32 meshes: no written-slot masks
+    small, large = (fu.rays(sc, fu.random(1)(n, sc.kinds)) for n in (300, 4160))
+    return lambda e: e.upload_arrays(*sc.arrs), small, large, fu.MAX_RAY_LEN, fu.IOR_ENV, 3, 0.0
+
+
+@pytest.mark.parametrize("case", [_lens_regrow, _fates_regrow], ids=["lens", "fates-K33"])
+def test_workspace_regrowth_resets_slot_and_group_state(case):
+    """A larger population makes the workspace grow: fresh slot arrays and group
+    words, so what the runtime remembers of them goes back to "dirty, buffer 0".
+    On one engine a 300-ray trace (unsorted: no key kernel to carry the reset), a
+    4 160-ray trace (the workspace grows; sorted, the reset rides on the key
+    kernel), the same again (its chained iterations run device-sized) and the
+    300-ray trace again each equal the same trace on a fresh engine: counts per
+    iteration, measured count, per-mesh power bit for bit, over every ray."""
+    from lightpycl_amd.engine import Engine
+    upload, small, large, mrl, ior, iters, thr = case()
+    assert len(small[2]) == 300 and len(large[2]) == 4160
+
+    def trace(e, rays):
+        e.set_rays(*rays, mrl, ior)
+        stats, (cnt, mp) = e.run_local(iters, thr)
+        return [(s.n_in, s.n_reflect, s.n_refract, s.n_measured) for s in stats], int(cnt), np.array(mp)
+
+    fresh = []
+    for rays in (small, large):
+        e = Engine(0)
+        try:
+            upload(e)
+            fresh.append(trace(e, rays))
+        finally:
+            e.close()
+    e = Engine(0)
+    try:
+        upload(e)
+        got = [trace(e, rays) for rays in (small, large, large, small)]
+    finally:
+        e.close()
+    for k, (g, want) in enumerate(zip(got, (fresh[0], fresh[1], fresh[1], fresh[0]))):
+        assert len(want[0]) >= 2 and want[0][0][0] == (300, 4160, 4160, 300)[k], k
+        assert g[0] == want[0] and g[1] == want[1], k
+        np.testing.assert_array_equal(g[2], want[2], err_msg=f"trace {k}")
+
+
 def test_dropin_calls_between_iterations_leave_trace_alone():
     """A bounce and an lpc_intersect drop-in call on the handle between every two
     trace iterations (few meshes: the written-slot masks are on) change nothing
