@@ -468,6 +468,46 @@ int lpc_trace_set_budget(lpc_handle *h, int on);
 int lpc_trace_budget(lpc_handle *h, lpc_budget_iter *per_iter, int32_t iter_cap, int32_t *n_iter,
                      double *mesh_power, int64_t *mesh_count, int32_t mesh_cap);
 
+/* ---- surface map ---------------------------------------------------------- */
+/* Opt-in (default off: every result keeps its bits and the kernels launched are
+ * the ones launched without it).  Per triangle of the scene, where the trace's
+ * power landed.  A triangle i is an index into the flattened triangle array of
+ * lpc_scene_upload: the reference's isect_idx.  For every traced ray of every
+ * iteration whose nearest hit exists (hit mesh >= 0, hence triangle >= 0), with
+ * p the ray's power after dissipation and kr / kt the kept children's powers as
+ * the power budget defines them (a child's power where the shading kept that
+ * child, else 0, before any cutoff), all in float64 formed from the float32
+ * values:
+ *   incident   (double)p                          every hit, whatever the material
+ *   count      1                                  every such hit (exact)
+ *   deposited  (double)p                          hit mesh of type 2 (terminator) or 3 (measure)
+ *              ((double)p - (double)kr) - (double)kt   every other hit mesh
+ * `deposited` is the power budget's per-mesh term of that hit: for each mesh, the
+ * sum of `deposited` over its triangles is the budget's absorbed + terminated +
+ * measured of that mesh, and the counts sum to the budget's three counts.  Rays
+ * that hit nothing and the dissipation inside a medium have no triangle and are
+ * not booked.  NaN powers propagate into the sums.  A triangle index outside the
+ * scene (never expected) is skipped.  The counts are exact; the float64 sums are
+ * added with atomics and may differ in their last bits from run to run. */
+/* Entries of the direct-mapped table in which a block of k_surface_sum merges its
+ * adds (keyed by triangle % entries; tests build conflicting targets from it). */
+#define LPC_SURFACE_LDS_ENTRIES 1024
+/* on != 0: the map is kept.  Holds until changed, from the next launched
+ * iteration.  Applies to every trace path (as lpc_trace_set_min_power), not to
+ * the per-kernel drop-ins or lpc_bounce_host.  Independent of the power budget:
+ * with the map on and the budget off, lpc_trace_budget reports what it reports
+ * without the map. */
+int lpc_trace_set_surface(lpc_handle *h, int on);
+/* The map of the current trace, summed over its iterations.  *tri_count: the
+ * scene's triangle count, always written.  incident / deposited / count
+ * (tri_count entries each, any may be NULL); tri_cap < tri_count with one of them
+ * given: LPC_E_ARG, no array is written.  Zeros for a trace that ran with the map
+ * off.  Cleared wherever the measured record is (set_rays, reset, rerun,
+ * run_staged, set_rays_dev).  Waits for the stream.  LPC_E_STATE without a
+ * scene. */
+int lpc_trace_surface(lpc_handle *h, double *incident, double *deposited, int64_t *count, int64_t tri_cap,
+                      int64_t *tri_count);
+
 /* ---- diagnostics ---------------------------------------------------------- */
 /* The device's own conservative-filter code on n (ray, record) pairs, host
  * arrays: origin3/dir3 (n,3), rec5 (n,5) = centre xyz, negB, negA (filter_record /

@@ -31,6 +31,8 @@ class IterStats(ctypes.Structure):
 BUDGET_SUMS = ("power_in", "dissipated", "escaped", "terminated", "measured", "absorbed", "kept")
 BUDGET_COUNTS = ("n_in", "n_dissipated", "n_escaped", "n_terminated", "n_measured", "n_absorbed")
 BUDGET_MESH = ("dissipated", "absorbed", "terminated", "measured")       # the per-mesh table's columns
+SURFACE_COLUMNS = ("incident", "deposited", "count")                     # the surface map's per-triangle columns
+SURFACE_LDS_ENTRIES = 1024      # include/lpc.h LPC_SURFACE_LDS_ENTRIES (k_surface_sum's block table)
 
 
 class BudgetIter(ctypes.Structure):
@@ -129,6 +131,8 @@ _PROTOS = {
     "lpc_trace_culled": [_P, _P, _P, _I32, _P],
     "lpc_trace_set_budget": [_P, _INT],
     "lpc_trace_budget": [_P, _P, _I32, _P, _P, _P, _I32],
+    "lpc_trace_set_surface": [_P, _INT],
+    "lpc_trace_surface": [_P, _P, _P, _P, _I64, _P],
 }
 
 # lpc_allreduce_fn (include/lpc.h): int (*)(void *ctx, double *vals, int32_t n)

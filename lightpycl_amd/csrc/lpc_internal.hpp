@@ -183,6 +183,12 @@ struct BudgetRec {                    // [chunk rays] each (SoA)
     float *pin, *p;                   // the power as read, after dissipation (ShadeOut::pow)
     float *kr, *kt;                   // the kept children's powers as the shading wrote them (not kept: 0)
 };
+// The record's seventh array, the hit triangle (PostOut::hit_idx), exists only
+// with the surface map on.  It travels beside BudgetRec, not in it: StageArgs
+// embeds BudgetRec, and the kernels that never write a record keep their code
+// only while their argument block keeps its size (a larger block changed the
+// device-sized instantiations).  The seven arrays are one allocation at one
+// stride, so k_shade_stage finds the seventh from a flag (StageArgs::bud_tri).
 #define LPC_BUD_SUMS 7                    // power_in, dissipated, escaped, terminated, measured, absorbed, kept
 #define LPC_BUD_CNTS 6                    // n_in, n_dissipated, n_escaped, n_terminated, n_measured, n_absorbed
 #define LPC_BUD_LDS_MESHES 64             // meshes whose [4] table rows a block keeps in LDS (more: global atomics)
@@ -199,6 +205,22 @@ struct BudgetSumArgs {
     BudgetRow *row;                   // the iteration's row (zeroed before its first chunk)
     double *mp;                       // [K][4] staging table of the iteration: dissipated, absorbed,
     unsigned long long *mc;           //   terminated, measured (zeroed before its first chunk)
+};
+// The surface map (lpc_trace_surface): k_surface_sum books
+// the same fate records per hit triangle into the iteration's staging table,
+// k_surface_commit adds a collected iteration's staging table to the trace's.
+// A table is three columns of tri_count entries: incident, deposited, count.
+#define LPC_SURF_LDS 1024                 // entries of a block's direct-mapped LDS table (lpc.h: LPC_SURFACE_LDS_ENTRIES)
+#define LPC_SURF_ROUNDS 4                 // leader rounds of the merge inside a wave
+struct SurfaceSumArgs {
+    BudgetRec R;                      // (hit, p, kr, kt are read)
+    const int32_t *tri;               // the records' seventh array
+    int64_t n;                        // records of the launch (device-sized: its bound)
+    const long long *nd;              // device-sized launch: the records (NULL: n)
+    const int32_t *mat_type;
+    int32_t K, M;                     // meshes, triangles
+    double *inc, *dep;                // [M] staging columns of the iteration (zeroed before its first chunk)
+    unsigned long long *cnt;          // [M]
 };
 
 struct CompactArgs {
@@ -259,6 +281,8 @@ struct StageArgs {
                                       //   max xyz), or NULL: the next population's coherence key box
     // power cutoff (the CUT instantiations only): see CompactArgs
     float cut;
+    uint32_t bud_tri;                 // BUD only, surface map on: the records hold a seventh array behind
+                                      //   bud.kt at stride cst (these four bytes were padding)
     uint32_t *tcc;                    // [ntiles] culled children
     double *tcp;                      // [ntiles] their power
     // power budget (the BUD instantiations only): the chunk's fate records

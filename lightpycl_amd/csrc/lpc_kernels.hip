@@ -1546,8 +1546,8 @@ __global__ __launch_bounds__(256) void k_shade(ShadeArgs A)
 // The power budget's fate record of ray r (BudgetRec; lpc.h has the ledger's
 // rule): pin is the power the shading read, po / s what it made of the ray.  The
 // dissipation test is shade()'s own (.cl:385-394).
-static __device__ __forceinline__ void budget_record(const BudgetRec &B, const ShadeArgs &A, int64_t r, float pin,
-                                                     const PostOut &po, const ShadeOut &s)
+static __device__ __forceinline__ void budget_record(const BudgetRec &B, int32_t *tri, const ShadeArgs &A, int64_t r,
+                                                     float pin, const PostOut &po, const ShadeOut &s)
 {
     const bool dis = po.n1 >= 0 && A.mat_type[po.n1] == 0 && A.diss[po.n1] > 0.000001f;
     B.dn[r] = dis ? po.n1 : -1;
@@ -1556,19 +1556,20 @@ static __device__ __forceinline__ void budget_record(const BudgetRec &B, const S
     B.p[r] = s.pow;
     B.kr[r] = s.r_meas == 0 ? s.r_pow : 0.0f;
     B.kt[r] = s.t_meas == 0 ? s.t_pow : 0.0f;
+    if (tri) tri[r] = po.hit_idx;       // the surface map's seventh array
 }
 
 // k_shade with the power budget on: the same shading and stores, and the ray's
 // fate record.
 template <int KU>
-__global__ __launch_bounds__(256) void k_shade_bud(ShadeArgs A, BudgetRec B)
+__global__ __launch_bounds__(256) void k_shade_bud(ShadeArgs A, BudgetRec B, int32_t *tri)
 {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= A.n) return;
     const float pin = A.in.pw[r];
     PostOut po;
     const ShadeOut s = shade_ray<KU>(A, r, &po);
-    budget_record(B, A, r, pin, po, s);
+    budget_record(B, tri, A, r, pin, po, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -1822,7 +1823,8 @@ static __device__ __forceinline__ int tile_tid()
 // count and power (tcc / tcp) feed the ledger (k_cull_sum).  Its extra wave sums
 // and per-tile arrays exist only in that instantiation.
 // BUD: the power budget's instantiation (lpc_trace_set_budget): every ray's fate
-// record (six stores, taken before the cutoff) for k_budget_sum.
+// record (six stores, taken before the cutoff) for k_budget_sum; with the surface
+// map on (lpc_trace_set_surface) a seventh, the hit triangle, for k_surface_sum.
 template <int KU, bool DS, bool CUT = false, bool BUD = false>
 __global__ __launch_bounds__(LPC_ST_TILE) void k_shade_stage(StageArgs A)
 {
@@ -1878,7 +1880,8 @@ __global__ __launch_bounds__(LPC_ST_TILE) void k_shade_stage(StageArgs A)
         }
     }
     if constexpr (BUD) {
-        if (in) budget_record(A.bud, S, r, S.in.pw[r], po, s);
+        // (the seventh array lies behind the sixth, at the records' stride)
+        if (in) budget_record(A.bud, A.bud_tri ? (int32_t *)(A.bud.kt + A.cst) : nullptr, S, r, S.in.pw[r], po, s);
     }
     bool fR = in && s.r_meas == 0, fT = in && s.t_meas == 0;
     const bool fM = in && s.meas == 1;
@@ -2434,6 +2437,109 @@ __global__ __launch_bounds__(256) void k_budget_commit(double *mp_tot, unsigned 
 {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
         if (mc[i]) { mp_tot[i] += mp[i]; mc_tot[i] += mc[i]; }
+}
+
+// The surface map of one chunk: its fate records booked per hit triangle into
+// the iteration's staging table (lpc.h has the terms).  Populations come in
+// coherence or traced order, so the lanes of a wave often share a triangle, and
+// a collimated beam puts a whole launch on two: adds merge in three stages
+// before they reach memory.
+//   1. In a wave: up to LPC_SURF_ROUNDS rounds, each of which takes the first
+//      lane not yet merged as leader, ballots the lanes with the leader's
+//      triangle and sums their terms into the leader (masked wave sums; a
+//      leader alone in its ballot keeps its own terms, no sum).  Lanes still
+//      unmerged after the rounds carry their own terms on.
+//   2. In a block, over its grid-stride steps: a direct-mapped LDS table keyed by
+//      tri % LPC_SURF_LDS.  A lane claims its entry by compare-and-swap on the
+//      tag (-1: free) and adds there; an entry owned by another triangle sends
+//      the lane's terms to the global table directly.
+//   3. The block adds its claimed entries to the global table once, at its end.
+// All rays on one triangle therefore cost three global atomics per block, not
+// per ray; every ray on its own triangle costs LPC_SURF_ROUNDS ballots, no sum.
+// Counts are exact; the float64 sums depend on the adds' order in their last
+// bits.  A tri outside [0, M) is skipped.
+__global__ __launch_bounds__(256) void k_surface_sum(SurfaceSumArgs A)
+{
+    __shared__ double s_inc[LPC_SURF_LDS];
+    __shared__ double s_dep[LPC_SURF_LDS];
+    __shared__ int32_t s_tag[LPC_SURF_LDS];
+    __shared__ unsigned int s_cnt[LPC_SURF_LDS];
+    const int t = threadIdx.x, lane = t & 63;
+    int64_t n = A.n;
+    if (A.nd) {
+        const long long nd = *A.nd;
+        n = nd > 0 ? min((int64_t)nd, A.n) : 0;
+    }
+    for (int i = t; i < LPC_SURF_LDS; i += 256) { s_inc[i] = 0.0; s_dep[i] = 0.0; s_tag[i] = -1; s_cnt[i] = 0u; }
+    __syncthreads();
+    // (whole waves take every step: the ballots and shuffles below need all lanes)
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < n; base += (int64_t)gridDim.x * 256) {
+        const int64_t r = base + t;
+        int32_t tri = -1;
+        double inc = 0.0, dep = 0.0;
+        unsigned int cnt = 0u;
+        if (r < n) {
+            const int32_t hit = A.R.hit[r];
+            const int32_t ti = A.tri[r];
+            if (hit >= 0 && (uint32_t)ti < (uint32_t)A.M) {
+                const double p = (double)A.R.p[r];
+                const int32_t mt = hit < A.K ? A.mat_type[hit] : -1;
+                tri = ti;
+                inc = p;
+                dep = (mt == 2 || mt == 3) ? p : (p - (double)A.R.kr[r]) - (double)A.R.kt[r];
+                cnt = 1u;
+            }
+        }
+        // 1. merge inside the wave
+        bool open = tri >= 0;                    // terms not yet merged into a leader
+        bool mine = open;                        // this lane carries terms on
+        for (int round = 0; round < LPC_SURF_ROUNDS; ++round) {
+            const unsigned long long todo = __ballot(open);
+            if (!todo) break;
+            const int lead = __builtin_ctzll(todo);
+            const int32_t lt = __shfl(tri, lead, 64);
+            const bool same = open && tri == lt;
+            const unsigned long long grp = __ballot(same);
+            if (grp & (grp - 1)) {               // more lanes than the leader
+                const double si = wave_sum(same ? inc : 0.0);
+                const double sd = wave_sum(same ? dep : 0.0);
+                const unsigned int sc = (unsigned int)__popcll(grp);
+                if (lane == lead) { inc = si; dep = sd; cnt = sc; }
+                else if (same) mine = false;
+            }
+            if (same) open = false;
+        }
+        // 2. merge in the block's table, or straight to the global one
+        if (mine) {
+            const int e = tri & (LPC_SURF_LDS - 1);
+            const int32_t old = atomicCAS(&s_tag[e], -1, tri);
+            if (old == -1 || old == tri) {
+                atomicAdd(&s_inc[e], inc); atomicAdd(&s_dep[e], dep); atomicAdd(&s_cnt[e], cnt);
+            } else {
+                atomicAdd(&A.inc[tri], inc); atomicAdd(&A.dep[tri], dep);
+                atomicAdd(&A.cnt[tri], (unsigned long long)cnt);
+            }
+        }
+    }
+    // 3. the block's entries, once
+    __syncthreads();
+    for (int i = t; i < LPC_SURF_LDS; i += 256) {
+        const int32_t tri = s_tag[i];
+        if (tri >= 0) {
+            atomicAdd(&A.inc[tri], s_inc[i]); atomicAdd(&A.dep[tri], s_dep[i]);
+            atomicAdd(&A.cnt[tri], (unsigned long long)s_cnt[i]);
+        }
+    }
+}
+
+// A collected iteration's per-triangle staging table into the trace's (the rule
+// of k_budget_commit: only iterations the trace keeps are added).
+__global__ __launch_bounds__(256) void k_surface_commit(double *inc_tot, double *dep_tot, unsigned long long *cnt_tot,
+                                                        const double *inc, const double *dep,
+                                                        const unsigned long long *cnt, int n)
+{
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
+        if (cnt[i]) { inc_tot[i] += inc[i]; dep_tot[i] += dep[i]; cnt_tot[i] += cnt[i]; }
 }
 
 // Population copy (trace reset: emitted rays -> current population), one launch.

@@ -304,10 +304,17 @@ struct lpc_handle {
     DBuf d_bud;                                     // BudgetRow[kCullSlots]: one per iteration of the trace
     DBuf d_bud_mesh;                                // per-mesh tables [3][K][4]: the trace's, two staging (iteration
                                                     //   parity); the float64 sums, then the counts
-    DBuf w_bud;                                     // fate records of one chunk (BudgetRec: 6 arrays of ws_rays)
+    DBuf w_bud;                                     // fate records of one chunk (BudgetRec: 6 arrays of ws_rays, 7
+                                                    //   with the surface map on)
     int32_t bud_K = 0;                              // the mesh count d_bud_mesh is laid out for
     bool bud_dirty = false;                         // the ledger may be non-zero (cleared with the measured record)
     bool bud_seen = false;                          // an iteration since the ledger was cleared ran with it on
+    // surface map (lpc_trace_set_surface) and its tables (lpc_trace_surface)
+    bool surface = false;                           // off: no seventh fate array, no k_surface_sum
+    DBuf d_surf;                                    // per-triangle tables [3][3][M]: the trace's, two staging (iteration
+                                                    //   parity); each incident, deposited (float64), count
+    int32_t surf_M = 0;                             // the triangle count d_surf is laid out for
+    bool surf_dirty = false;                        // the tables may be non-zero (cleared with the measured record)
     // trace
     Pop A, B, T, I;
     PopState pop;                                   // which of them is current, and as what
@@ -2064,6 +2071,10 @@ int lpc_trace_reset(lpc_handle *h)
         h->bud_dirty = false;
     }
     h->bud_seen = false;
+    if (h->surf_dirty) {                            // and the surface map
+        if (h->d_surf.p) HIPCHK(h, hipMemsetAsync(h->d_surf.p, 0, h->d_surf.bytes, h->stream));
+        h->surf_dirty = false;
+    }
     return 0;
 }
 
@@ -2333,6 +2344,40 @@ int lpc_trace_budget(lpc_handle *h, lpc_budget_iter *per_iter, int32_t iter_cap,
     return 0;
 }
 
+int lpc_trace_set_surface(lpc_handle *h, int on)
+{
+    if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
+    h->surface = on != 0;               // from the next launched iteration
+    return 0;
+}
+
+static_assert(LPC_SURF_LDS == LPC_SURFACE_LDS_ENTRIES, "lpc.h states k_surface_sum's LDS table size");
+static_assert((LPC_SURF_LDS & (LPC_SURF_LDS - 1)) == 0, "k_surface_sum maps a triangle by its low bits");
+
+int lpc_trace_surface(lpc_handle *h, double *incident, double *deposited, int64_t *count, int64_t tri_cap,
+                      int64_t *tri_count)
+{
+    if (!h || !tri_count) return set_err(h, LPC_E_ARG, "null argument");
+    RETIF(need_scene(h));
+    const int64_t M = h->scene.M;
+    *tri_count = M;                     // (also where the arrays are refused: the caller learns the size)
+    if ((incident || deposited || count) && tri_cap < M)
+        return set_err(h, LPC_E_ARG, "trace_surface: triangle capacity below the scene's triangle count");
+    RETIF(settle(h));
+    const size_t m = (size_t)M;
+    if (incident) memset(incident, 0, m * sizeof(double));
+    if (deposited) memset(deposited, 0, m * sizeof(double));
+    if (count) memset(count, 0, m * sizeof(int64_t));
+    if (!h->surf_dirty || !h->d_surf.p || h->surf_M != h->scene.M || m == 0) return 0;
+    HIPCHK(h, hipSetDevice(h->device));
+    const char *d = (const char *)h->d_surf.p;                  // the trace's table: the first three columns
+    if (incident) HIPCHK(h, hipMemcpyAsync(incident, d, m * 8, hipMemcpyDeviceToHost, h->stream));
+    if (deposited) HIPCHK(h, hipMemcpyAsync(deposited, d + m * 8, m * 8, hipMemcpyDeviceToHost, h->stream));
+    if (count) HIPCHK(h, hipMemcpyAsync(count, d + 2 * m * 8, m * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
 int lpc_shm_comm_open(const char *name, int32_t rank, int32_t world, int32_t create, lpc_shm_comm **out)
 {
     if (!out) return set_err(nullptr, LPC_E_ARG, "shm comm: null output");
@@ -2445,6 +2490,8 @@ struct Pending {
     double thr = -INFINITY;     // fused: the stop threshold its k_stage_move applied (IterPlan::thr)
     bool bud = false;           // it ran with the power budget on: its per-mesh staging table ...
     int bpar = 0;               // ... of this parity joins the trace's when it is collected
+    bool surf = false;          // it ran with the surface map on: its per-triangle staging table likewise
+    int spar = 0;
     PopState before;            // the population's role before its enqueue (undo of a discarded speculative iteration)
 };
 
@@ -2550,8 +2597,12 @@ struct IterPlan {
     bool want_box = false;                  // fused: the chunks write the children's origin box (d_pbox)
     bool cut = false;                       // power cutoff: the compaction's CUT instantiations ...
     CullSumArgs CS;                         // ... and the ledger's arguments (both cull_setup's)
-    bool bud = false;                       // power budget: the shading's BUD instantiations ...
-    BudgetSumArgs BS;                       // ... and the ledger's arguments (both budget_setup's)
+    bool bud = false;                       // power budget: k_budget_sum runs, with the ledger's arguments ...
+    BudgetSumArgs BS;                       // ... (budget_setup's; BS.R: the fate records, budget or surface map)
+    int32_t *bud_tri = nullptr;             // the records' seventh array (surface map on, else NULL)
+    bool surf = false;                      // surface map: k_surface_sum runs, with ...
+    SurfaceSumArgs SS;                      // ... the map's arguments (surface_setup's)
+    bool rec() const { return bud || surf; }    // the shading's BUD instantiations write the fate records
 };
 
 // Power cutoff: this launch's per-tile culled sums and the iteration's ledger
@@ -2584,12 +2635,22 @@ static int cull_setup(lpc_handle *h, IterPlan *I)
 // cull_setup) and its per-mesh staging table, both zeroed here, before the
 // iteration's first chunk: an iteration that is re-run starts from zero again,
 // and a dropped speculative iteration's sums never reach the trace's table
-// (iter_collect adds a kept iteration's).  Off: I->BS stays zero.
+// (iter_collect adds a kept iteration's).  Off: I->BS stays zero, but for the
+// records when the surface map (surface_setup) needs them.
 static int budget_setup(lpc_handle *h, IterPlan *I, Pending *P)
 {
     BudgetSumArgs *BS = &I->BS;
     memset(BS, 0, sizeof(*BS));
     I->bud = h->budget;
+    I->bud_tri = nullptr;
+    if (h->budget || h->surface) {      // the fate records: six arrays, and the triangle with the surface map on
+        const size_t C = (size_t)h->ws_rays;
+        RETIF(dalloc(h, h->w_bud, (h->surface ? 7 : 6) * C * 4));
+        float *f = (float *)h->w_bud.p;
+        BS->R.dn = (int32_t *)f; BS->R.hit = (int32_t *)(f + C);
+        BS->R.pin = f + 2 * C; BS->R.p = f + 3 * C; BS->R.kr = f + 4 * C; BS->R.kt = f + 5 * C;
+        if (h->surface) I->bud_tri = (int32_t *)(f + 6 * C);
+    }
     if (!I->bud) return 0;
     const int64_t slot = h->it_done + (I->ds ? 1 : 0);
     if (slot >= kCullSlots)
@@ -2606,11 +2667,6 @@ static int budget_setup(lpc_handle *h, IterPlan *I, Pending *P)
         HIPCHK(h, hipMemsetAsync(h->d_bud_mesh.p, 0, h->d_bud_mesh.bytes, h->stream));
         h->bud_K = K;
     }
-    const size_t C = (size_t)h->ws_rays;
-    RETIF(dalloc(h, h->w_bud, 6 * C * 4));
-    float *f = (float *)h->w_bud.p;
-    BS->R.dn = (int32_t *)f; BS->R.hit = (int32_t *)(f + C);
-    BS->R.pin = f + 2 * C; BS->R.p = f + 3 * C; BS->R.kr = f + 4 * C; BS->R.kt = f + 5 * C;
     BS->mat_type = (const int32_t *)h->scene.d_mat.p;
     BS->K = K;
     BS->row = (BudgetRow *)h->d_bud.p + slot;
@@ -2649,6 +2705,63 @@ static int budget_commit(lpc_handle *h, const Pending &P)
     hipLaunchKernelGGL(k_budget_commit, dim3(nb), dim3(256), 0, h->stream, mp, mc,
                        (const double *)(mp + (size_t)(1 + P.bpar) * kt),
                        (const unsigned long long *)(mc + (size_t)(1 + P.bpar) * kt), (int)kt);
+    HIPCHK(h, hipGetLastError());
+    h->inflight = true;
+    return 0;
+}
+
+// Surface map (after budget_setup, whose records it reads): the per-triangle
+// tables and the iteration's staging table, chosen by the slot's parity and
+// zeroed here, before the iteration's first chunk -- budget_setup's rules.
+// Off: I->SS stays zero.
+static int surface_setup(lpc_handle *h, IterPlan *I, Pending *P)
+{
+    SurfaceSumArgs *SS = &I->SS;
+    memset(SS, 0, sizeof(*SS));
+    I->surf = h->surface;
+    if (!I->surf) return 0;
+    const int32_t M = h->scene.M;
+    const size_t m = (size_t)M;
+    if (!h->d_surf.p || h->surf_M != M) {
+        // (a scene with another triangle count comes with new rays: the tables were cleared)
+        RETIF(dalloc(h, h->d_surf, 9 * m * 8));
+        HIPCHK(h, hipMemsetAsync(h->d_surf.p, 0, h->d_surf.bytes, h->stream));
+        h->surf_M = M;
+    }
+    const int64_t slot = h->it_done + (I->ds ? 1 : 0);
+    const int par = (int)(slot & 1);
+    double *st = (double *)h->d_surf.p + (size_t)(1 + par) * 3 * m;
+    SS->R = I->BS.R; SS->tri = I->bud_tri;
+    SS->mat_type = (const int32_t *)h->scene.d_mat.p;
+    SS->K = h->scene.K; SS->M = M;
+    SS->inc = st; SS->dep = st + m; SS->cnt = (unsigned long long *)(st + 2 * m);
+    if (m > 0) HIPCHK(h, hipMemsetAsync(st, 0, 3 * m * 8, h->stream));
+    h->surf_dirty = true;
+    P->surf = true;
+    P->spar = par;
+    return 0;
+}
+
+// Surface map: the chunk's records into the iteration's staging table.
+static void surface_sum(lpc_handle *h, const IterPlan &I, int64_t nc, const long long *nd)
+{
+    SurfaceSumArgs SS = I.SS;
+    SS.n = nc; SS.nd = nd;
+    const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>((nc + 255) / 256, 1024));
+    hipLaunchKernelGGL(k_surface_sum, dim3(nb), dim3(256), 0, h->stream, SS);
+}
+
+// Surface map: a collected iteration's staging table into the trace's.
+static int surface_commit(lpc_handle *h, const Pending &P)
+{
+    if (!P.surf || P.empty || !h->d_surf.p || h->surf_M == 0) return 0;
+    const size_t m = (size_t)h->surf_M;
+    double *tot = (double *)h->d_surf.p;
+    const double *st = tot + (size_t)(1 + P.spar) * 3 * m;
+    const unsigned nb = (unsigned)std::min<size_t>((m + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_surface_commit, dim3(nb), dim3(256), 0, h->stream, tot, tot + m,
+                       (unsigned long long *)(tot + 2 * m), st, st + m, (const unsigned long long *)(st + 2 * m),
+                       (int)m);
     HIPCHK(h, hipGetLastError());
     h->inflight = true;
     return 0;
@@ -2697,7 +2810,7 @@ static int enqueue_fused_chunk(lpc_handle *h, const IterPlan &I, const RaysIn &i
     G.tmask = tmask;
     G.tbox = I.want_box ? (uint32_t *)h->w_tbox.p : nullptr;
     G.cut = h->min_power; G.tcc = (uint32_t *)I.CS.cc; G.tcp = (double *)I.CS.cp;
-    G.bud = I.BS.R;
+    G.bud = I.BS.R; G.bud_tri = I.bud_tri ? 1u : 0u;       // (the records' stride is cst: both are ws_rays)
     // (this nesting keeps the instantiations in their order in the code object;
     // the power budget's come after the others)
     auto launch_stage = [&](auto bud) {
@@ -2711,7 +2824,7 @@ static int enqueue_fused_chunk(lpc_handle *h, const IterPlan &I, const RaysIn &i
             });
         });
     };
-    if (!I.bud) launch_stage(std::false_type{});
+    if (!I.rec()) launch_stage(std::false_type{});
     else launch_stage(std::true_type{});
     MoveArgs M;
     M.ntiles = nt_max; M.ngroups = ng;
@@ -2743,6 +2856,7 @@ static int enqueue_fused_chunk(lpc_handle *h, const IterPlan &I, const RaysIn &i
     });
     if (I.cut) cull_sum(h, I, base, nt_max, LPC_ST_TILE, I.nd());
     if (I.bud) budget_sum(h, I, nc, I.nd());
+    if (I.surf) surface_sum(h, I, nc, I.nd());
     // k_shade_stage restored what it read, k_stage_move reset the next launch's words
     h->slots = SlotState{/*clean*/ true, h->emitted.max_ray_len, /*misc_clean*/ true};
     HIPCHK(h, hipGetLastError());
@@ -2789,13 +2903,15 @@ static int enqueue_plain_chunk(lpc_handle *h, const IterPlan &I, const IterOut &
     A.host_acc = I.host_acc;
     A.seq = I.seq;
     A.cut = h->min_power; A.blk_cc = (uint32_t *)I.CS.cc; A.blk_cp = (double *)I.CS.cp;
-    if (I.bud) {                        // k_shade with the fate records, and their sums
+    if (I.rec()) {                      // k_shade with the fate records, and their sums
         const ShadeArgs SA = shade_args(h, in, nullptr, nc, h->emitted.max_ray_len, h->emitted.ior_env, false);
         with_ku(h->scene.K, [&](auto ku) {
-            hipLaunchKernelGGL(k_shade_bud<decltype(ku)::value>, dim3(grid1(nc)), dim3(256), 0, h->stream, SA, I.BS.R);
+            hipLaunchKernelGGL(k_shade_bud<decltype(ku)::value>, dim3(grid1(nc)), dim3(256), 0, h->stream, SA, I.BS.R,
+                               I.bud_tri);
         });
         HIPCHK(h, hipGetLastError());
-        budget_sum(h, I, nc, nullptr);
+        if (I.bud) budget_sum(h, I, nc, nullptr);
+        if (I.surf) surface_sum(h, I, nc, nullptr);
     } else {
         RETIF(run_shade(h, in, nullptr, nc, h->emitted.max_ray_len, h->emitted.ior_env, false));
     }
@@ -2844,6 +2960,7 @@ static int iter_enqueue(lpc_handle *h, const IterOut &O, const DevSize *ds, doub
     RETIF(ensure_measured(h, h->m_total + h->m_inflight + N));
     RETIF(cull_setup(h, &I));
     RETIF(budget_setup(h, &I, P));
+    RETIF(surface_setup(h, &I, P));
     if (h->knobs.host_prof)
         fprintf(stderr, "[lpc host]   buffers %.1f us (m_total %lld inflight %lld m_cap %lld)\n", host_us() - hp0,
                 (long long)h->m_total, (long long)h->m_inflight, (long long)h->m_cap);
@@ -2919,6 +3036,7 @@ static int iter_collect(lpc_handle *h, const Pending &P, float *out_next_pow, lp
     ++h->it_done;                       // the ledger's slot count (an empty iteration's slot stays zero)
     if (P.empty) { if (st) *st = S; return 0; }
     RETIF(budget_commit(h, P));
+    RETIF(surface_commit(h, P));
     DevAcc acc;
     const double t_wait = h->knobs.host_prof ? host_us() : 0.0;
     if (P.early) {

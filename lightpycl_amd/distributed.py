@@ -149,6 +149,9 @@ class ShmComm:
             pass
 
 
+SURFACE_PIECE = 1 << 20     # float64 values per exchange of the surface map's tables (ShardedTrace.run)
+
+
 def shard_bounds(n, rank, world):
     """Contiguous shard [lo, hi) of n rays for `rank` (sizes differ by at most 1)."""
     q, r = divmod(n, world)
@@ -266,6 +269,21 @@ class ShardedTrace:
             g["mesh_power"] = tot[rows.size:rows.size + kk].reshape(-1, 4)
             g["mesh_count"] = np.rint(tot[rows.size + kk:]).astype(np.int64).reshape(-1, 4)
             out["power_budget"] = budget_dict(g, out.get("culled_counts", ()), out.get("culled_power", ()))
+        if getattr(self.engine, "surface_on", False):
+            # the surface map (Engine.set_surface, on every rank alike) summed over
+            # the ranks with the same comm: three tables of the scene's triangle
+            # count, a size that no rank's data changes, in pieces of at most
+            # SURFACE_PIECE values (a comm's payload is an int32 count of float64,
+            # and a piece keeps its buffers small); counts are exact in float64
+            s = self.engine.surface()
+            m = len(s["count"])
+            flat = np.concatenate((np.asarray(s["incident"], np.float64), np.asarray(s["deposited"], np.float64),
+                                   np.asarray(s["count"], np.float64)))
+            tot = np.empty_like(flat)
+            for lo in range(0, len(flat), SURFACE_PIECE):
+                tot[lo:lo + SURFACE_PIECE] = self._sum(flat[lo:lo + SURFACE_PIECE])
+            out["surface"] = {"incident": tot[:m].copy(), "deposited": tot[m:2 * m].copy(),
+                              "count": np.rint(tot[2 * m:]).astype(np.int64)}
         if hist is not None:
             limits, points = hist
             H, xe, ye = self.engine.project_hist(None, None, limits, points)[:3]

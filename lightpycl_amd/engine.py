@@ -198,6 +198,7 @@ class Engine:
         self.mesh_count = 0
         self.min_power = 0.0
         self.budget_on = False
+        self.surface_on = False
 
     # -- lifecycle -----------------------------------------------------------
     def close(self):
@@ -418,6 +419,24 @@ class Engine:
             out[name] = np.array([getattr(rows[i], name) for i in range(n.value)], np.int64)
         out["mesh_power"], out["mesh_count"] = mp, mc
         return out
+
+    def set_surface(self, on):
+        """lpc_trace_set_surface: keep the surface map (off by default); holds
+        until changed, from the next launched iteration."""
+        self._c(self.L.lpc_trace_set_surface(self.h, 1 if on else 0))
+        self.surface_on = bool(on)
+
+    def surface(self):
+        """lpc_trace_surface: the surface map of the current trace -> a dict of
+        three flat arrays over the scene's triangles (the order of the upload):
+        ``incident`` and ``deposited`` (float64), ``count`` (int64).  Zeros when
+        the trace ran with the map off."""
+        m = ctypes.c_int64(0)
+        self._c(self.L.lpc_trace_surface(self.h, None, None, None, 0, ctypes.byref(m)))
+        inc, dep = np.zeros(m.value, np.float64), np.zeros(m.value, np.float64)
+        cnt = np.zeros(m.value, np.int64)
+        self._c(self.L.lpc_trace_surface(self.h, ptr(inc), ptr(dep), ptr(cnt), m.value, ctypes.byref(m)))
+        return {"incident": inc, "deposited": dep, "count": cnt}
 
     def reset(self):
         self._c(self.L.lpc_trace_reset(self.h))

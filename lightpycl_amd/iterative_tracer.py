@@ -55,6 +55,60 @@ def f32_sorted_sum(a):
     return np.float32(out.value)
 
 
+def triangle_areas(mesh):
+    """Areas of a mesh's triangles in its own triangle order, ``0.5 |E1 x E2|``
+    in float64 from the mesh's vertices as they are held on the host (not the
+    float32 rows of the upload)."""
+    V, T = getattr(mesh, "vertices", None), getattr(mesh, "triangles", None)
+    try:
+        V = np.asarray(V, np.float64)
+        T = np.asarray(T)
+        ok = V.ndim == 2 and V.shape[1] >= 3 and T.ndim == 2 and T.shape[1] == 3 and T.dtype.kind in "iu"
+    except Exception:
+        ok = False
+    if ok:
+        a, b, c = (V[T[:, k], :3] for k in range(3))
+    else:                                       # general vertex containers: the reference's tribuf() lists
+        tb = mesh.tribuf()
+        a, b, c = (np.asarray(tb[k], np.float64).reshape(-1, 4)[:, :3] for k in range(3))
+    return 0.5 * np.linalg.norm(np.cross(b - a, c - a), axis=1)
+
+
+def surface_dict(s, meshes):
+    """The surface map as the tracer returns it, from ``Engine.surface()`` (or
+    the ranks' sum of it) and the traced meshes.
+
+    ``meshes``: per mesh, in the order of the trace's ``meshes``, a dict of
+    arrays in that mesh's own triangle order: ``incident`` (float64: the power of
+    every ray whose nearest hit is the triangle), ``deposited`` (float64: what
+    stayed there -- the whole ray on a terminator or measure mesh, else the ray
+    less its kept children: ``(1 - R) p`` on a mirror, the Fresnel split's
+    float32 residue on a refractive surface), ``count`` (int64 hits), ``area``
+    (:func:`triangle_areas`), ``irradiance`` = deposited / area and
+    ``incident_irradiance`` = incident / area (a zero-area sliver gives inf or
+    nan: it is not hidden), and ``offset``, the mesh's first triangle in the flat
+    arrays.  ``incident``, ``deposited``, ``count``: the flat arrays over all
+    triangles, the order of the scene upload (the reference's ``isect_idx``).
+    Per mesh, ``deposited`` sums to the power budget's absorbed + terminated +
+    measured of that mesh."""
+    inc, dep = np.asarray(s["incident"], np.float64), np.asarray(s["deposited"], np.float64)
+    cnt = np.asarray(s["count"], np.int64)
+    out = {"incident": inc, "deposited": dep, "count": cnt, "meshes": [], "offsets": []}
+    lo = 0
+    for m in meshes:
+        area = triangle_areas(m)
+        hi = lo + len(area)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["meshes"].append({"offset": lo, "incident": inc[lo:hi], "deposited": dep[lo:hi], "count": cnt[lo:hi],
+                                  "area": area, "irradiance": dep[lo:hi] / area,
+                                  "incident_irradiance": inc[lo:hi] / area})
+        out["offsets"].append(lo)
+        lo = hi
+    if lo != len(cnt):
+        raise ValueError(f"surface map: the meshes hold {lo} triangles, the scene {len(cnt)}")
+    return out
+
+
 def budget_dict(b, culled_counts=(), culled_power=()):
     """The power budget as the tracer returns it, from ``Engine.budget()`` and the
     culled-power ledger of the same trace (empty: no cutoff).
@@ -190,7 +244,7 @@ class CL_Tracer:
 
     def iterative_tracer(self, light_source, meshes, trace_iterations=100, trace_until_dissipated=0.99,
                          max_ray_len=np.float32(1e3), ior_env=np.float32(1.0), keep_results=True,
-                         min_ray_power=0.0, power_budget=False):
+                         min_ray_power=0.0, power_budget=False, surface_map=False):
         """Trace until ``trace_iterations`` bounces, until less than
         (1 - trace_until_dissipated) of the input power is left, or until no ray is
         left (iterative_tracer.py:241-391).  Returns ``self.results``.
@@ -212,12 +266,19 @@ class CL_Tracer:
         ``power_budget=True`` (default off; set on every call) keeps the trace's
         power budget on the device: where every ray's power went, per iteration
         and per mesh.  :meth:`power_budget` returns it afterwards (DESIGN.md
-        section 14).  The trace's results keep their bits with it on or off."""
+        section 14).  The trace's results keep their bits with it on or off.
+
+        ``surface_map=True`` (default off; set on every call) keeps the trace's
+        surface map on the device: the power incident on and deposited in every
+        triangle of the scene.  :meth:`surface_power` returns it afterwards
+        (DESIGN.md section 16).  The trace's results keep their bits likewise."""
         max_ray_len = np.float32(max_ray_len)
         ior_env = np.float32(ior_env)
         self.engine.set_min_power(min_ray_power)
         self.engine.set_budget(power_budget)
+        self.engine.set_surface(surface_map)
         self._budget = None
+        self._surface = None
         self.culled_counts, self.culled_power = [], []
         clk = time.perf_counter
         ph = {}                                 # host-side phases of this call (self.phase_s)
@@ -314,6 +375,7 @@ class CL_Tracer:
             t_ph = clk()
             self._read_culled()
             self._read_budget()
+            self._read_surface()
         finally:
             self.engine.sync()                  # the exported results arrays are complete
         ph["sync"] = clk() - t_ph
@@ -338,6 +400,17 @@ class CL_Tracer:
         self._budget = None
         if self.engine.budget_on:
             self._budget = budget_dict(self.engine.budget(), self.culled_counts, self.culled_power)
+
+    def _read_surface(self):
+        """The trace's surface map (read only with the map on, as the budget)."""
+        self._surface = None
+        if self.engine.surface_on:
+            self._surface = surface_dict(self.engine.surface(), self.meshes)
+
+    def surface_power(self):
+        """The surface map of the last trace (``surface_map=True``), see
+        :func:`surface_dict`; None when the trace ran without it."""
+        return getattr(self, "_surface", None)
 
     def power_budget(self):
         """The power budget of the last trace (``power_budget=True``), see
@@ -401,6 +474,7 @@ class CL_Tracer:
             t_ph = clk()
             self._read_culled()
             self._read_budget()
+            self._read_surface()
         finally:
             self.engine.sync()
         ph["sync"] = clk() - t_ph

@@ -66,10 +66,11 @@ class TracePool:
 
     @staticmethod
     def _trace(e, origin, direction, power, max_ray_len, ior_env, iterations, tau, measured, min_ray_power=0.0,
-               power_budget=False):
+               power_budget=False, surface_map=False):
         p = np.asarray(power, np.float32).reshape(-1)
         e.set_min_power(min_ray_power)      # set for every batch: omitted = off
         e.set_budget(power_budget)          # likewise
+        e.set_surface(surface_map)
         e.set_rays(origin, direction, p, max_ray_len, ior_env)
         thr = (1.0 - float(tau)) * float(np.sum(p, dtype=np.float64))
         stats, (count, mesh_power) = e.run_local(int(iterations), thr)
@@ -84,10 +85,12 @@ class TracePool:
         if power_budget:
             from .iterative_tracer import budget_dict
             out["power_budget"] = budget_dict(e.budget(), out.get("culled_counts", ()), out.get("culled_power", ()))
+        if surface_map:
+            out["surface"] = e.surface()
         return out
 
     def submit(self, origin, direction, power, max_ray_len=1e3, ior_env=1.0, iterations=16, tau=0.99,
-               measured=False, min_ray_power=0.0, power_budget=False):
+               measured=False, min_ray_power=0.0, power_budget=False, surface_map=False):
         """Queue one batch (origin/direction (n,4) float32 rows, power (n,)):
         traced to the reference's termination (``iterations``, dissipated
         fraction ``tau``, iterative_tracer.py:383-391).  ``min_ray_power`` > 0:
@@ -95,13 +98,15 @@ class TracePool:
         holds the ledger (``culled_counts``, ``culled_power`` per iteration).
         ``power_budget=True``: the trace's power budget (Engine.set_budget) as
         ``power_budget`` of the result, the dict of ``CL_Tracer.power_budget()``.
+        ``surface_map=True``: the trace's surface map (Engine.set_surface) as
+        ``surface`` of the result, the dict of ``Engine.surface()``.
         Returns a Future."""
         fut = cf.Future()
         with self._lock:
             j = self._next
             self._next = (self._next + 1) % len(self.engines)
         self._q[j].put((fut, (origin, direction, power, max_ray_len, ior_env, iterations, tau, measured,
-                                float(min_ray_power), bool(power_budget))))
+                                float(min_ray_power), bool(power_budget), bool(surface_map))))
         return fut
 
     def close(self):
