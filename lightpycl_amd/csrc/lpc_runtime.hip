@@ -231,6 +231,50 @@ struct GroupWords {
     }
 };
 
+// ---- the ledgers of a trace (DESIGN.md section 17 has their life cycle) ------
+// A ledger's device memory, with whether it may be non-zero: lpc_trace_reset
+// clears what is dirty (ledgers_clear), the handle frees it.  As per-iteration
+// rows: kCullSlots of them, allocated once and zeroed, row i for slot i.
+struct LedgerBuf {
+    DBuf buf;
+    bool dirty = false;
+    template <class Row> Row *row(int64_t i) const { return (Row *)buf.p + i; }
+};
+// The trace's table beside two staging tables, [3 tables][cols][n] entries of 8
+// bytes: an iteration sums into the staging table of its slot's parity, zeroed
+// before its first chunk, and the table joins the trace's only when the
+// iteration is collected.
+struct StagedTable : LedgerBuf {
+    int cols;
+    int64_t n = -1;                                 // the entries per column it is laid out for
+    explicit StagedTable(int c) : cols(c) {}
+    size_t table() const { return (size_t)cols * (size_t)n; }
+    double *total() const { return (double *)buf.p; }
+    double *staging(int par) const { return total() + (size_t)(1 + par) * table(); }
+    double *col(double *t, int c) const { return t + (size_t)c * (size_t)n; }
+    bool live() const { return buf.p && n > 0; }
+};
+// Which ledgers an iteration runs with (the switches as they stood at its enqueue).
+struct LedgerSet {
+    bool cut = false, bud = false, surf = false;
+    bool rec() const { return bud || surf; }        // the shading's BUD instantiations write the fate records
+};
+struct Ledgers {
+    float min_power = 0.0f;                         // lpc_trace_set_min_power; 0: off (the compaction's default
+                                                    //   instantiations)
+    bool budget = false;                            // lpc_trace_set_budget; off: the shading's default instantiations
+    bool surface = false;                           // lpc_trace_set_surface; off: no seventh fate array
+    int64_t it_done = 0;                            // iterations collected since the trace's reset: the next slot
+    bool bud_seen = false;                          // an iteration since the reset was enqueued with the budget on
+    LedgerBuf cull;                                 // lpc_trace_culled: CullSlot rows
+    DBuf w_cull;                                    // per-tile culled counts / powers of one launch
+    LedgerBuf bud;                                  // lpc_trace_budget: BudgetRow rows ...
+    StagedTable bud_mesh{2};                        // ... and per mesh: power, count of [K][4]
+    StagedTable surf{3};                            // lpc_trace_surface: incident, deposited, count of [M]
+    DBuf w_rec;                                     // fate records of one chunk (BudgetRec: 6 arrays of ws_rays, 7
+                                                    //   with the surface map on): the budget or the map on
+};
+
 // Every GPU resource of the handle is held by an owner of lpc_resource.hpp and
 // goes with it; lpc_close names no member.  The one rule: members are destroyed
 // in reverse declaration order, so a stream is declared before everything that
@@ -293,28 +337,7 @@ struct lpc_handle {
     DBuf d_cbase;                                   // chunked traced iterations: running row bases (ping-pong)
     DBuf w_tbox, d_pbox;                            // per-tile boxes (k_shade_stage), the population's box (k_stage_move)
     double mp_last[LPC_MP_MAX] = {0, 0, 0, 0};
-    // per-ray power cutoff (lpc_trace_set_min_power) and its ledger (lpc_trace_culled)
-    float min_power = 0.0f;                         // 0: off (the default instantiations of the compaction kernels)
-    DBuf d_cull;                                    // CullSlot[kCullSlots]: one per iteration of the trace
-    DBuf w_cull;                                    // per-tile culled counts / powers of one launch
-    bool cull_dirty = false;                        // some slot may be non-zero (cleared with the measured record)
-    int64_t it_done = 0;                            // iterations collected since the trace's reset
-    // power budget (lpc_trace_set_budget) and its ledger (lpc_trace_budget)
-    bool budget = false;                            // off: the default instantiations of the shading kernels
-    DBuf d_bud;                                     // BudgetRow[kCullSlots]: one per iteration of the trace
-    DBuf d_bud_mesh;                                // per-mesh tables [3][K][4]: the trace's, two staging (iteration
-                                                    //   parity); the float64 sums, then the counts
-    DBuf w_bud;                                     // fate records of one chunk (BudgetRec: 6 arrays of ws_rays, 7
-                                                    //   with the surface map on)
-    int32_t bud_K = 0;                              // the mesh count d_bud_mesh is laid out for
-    bool bud_dirty = false;                         // the ledger may be non-zero (cleared with the measured record)
-    bool bud_seen = false;                          // an iteration since the ledger was cleared ran with it on
-    // surface map (lpc_trace_set_surface) and its tables (lpc_trace_surface)
-    bool surface = false;                           // off: no seventh fate array, no k_surface_sum
-    DBuf d_surf;                                    // per-triangle tables [3][3][M]: the trace's, two staging (iteration
-                                                    //   parity); each incident, deposited (float64), count
-    int32_t surf_M = 0;                             // the triangle count d_surf is laid out for
-    bool surf_dirty = false;                        // the tables may be non-zero (cleared with the measured record)
+    Ledgers led;                                    // the power cutoff, the power budget, the surface map
     // trace
     Pop A, B, T, I;
     PopState pop;                                   // which of them is current, and as what
@@ -450,6 +473,62 @@ static int dalloc(lpc_handle *h, DBuf &b, size_t bytes, bool keep = false)
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     b = std::move(nb);
+    return 0;
+}
+
+// A ledger's buffer of at least `bytes`, zeroed whole when fresh is set or it had to be allocated.
+static int ledger_shape(lpc_handle *h, LedgerBuf &b, size_t bytes, bool fresh = false)
+{
+    if (b.buf.p && !fresh) return 0;
+    RETIF(dalloc(h, b.buf, bytes));
+    HIPCHK(h, hipMemsetAsync(b.buf.p, 0, b.buf.bytes, h->stream));
+    return 0;
+}
+
+// A staged table laid out for n entries per column (another n: a scene of
+// another size, which comes with new rays: the table was cleared).
+static int staged_shape(lpc_handle *h, StagedTable &T, int64_t n)
+{
+    if (T.buf.p && T.n == n) return 0;
+    RETIF(ledger_shape(h, T, 3 * (size_t)T.cols * (size_t)n * 8, true));
+    T.n = n;
+    return 0;
+}
+
+static int staged_zero(lpc_handle *h, const StagedTable &T, int par)
+{
+    if (T.n > 0) HIPCHK(h, hipMemsetAsync(T.staging(par), 0, T.table() * 8, h->stream));
+    return 0;
+}
+
+// The trace's table to the host, column c into the c-th of dst (NULL: skipped),
+// n entries each: zeros when it holds nothing or is laid out for another n.
+static int staged_read(lpc_handle *h, const StagedTable &T, int64_t n, std::initializer_list<void *> dst)
+{
+    for (void *d : dst)
+        if (d) memset(d, 0, (size_t)n * 8);
+    if (!T.dirty) return 0;
+    HIPCHK(h, hipSetDevice(h->device));
+    int c = 0;
+    for (void *d : dst) {
+        if (d && T.live() && T.n == n)
+            HIPCHK(h, hipMemcpyAsync(d, T.col(T.total(), c), (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+        ++c;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// lpc_trace_reset: a new trace starts at slot 0 with every ledger zero.
+static int ledgers_clear(lpc_handle *h)
+{
+    Ledgers &G = h->led;
+    G.it_done = 0;
+    G.bud_seen = false;
+    for (LedgerBuf *b : std::initializer_list<LedgerBuf *>{&G.cull, &G.bud, &G.bud_mesh, &G.surf}) {
+        if (b->dirty && b->buf.p) HIPCHK(h, hipMemsetAsync(b->buf.p, 0, b->buf.bytes, h->stream));
+        b->dirty = false;
+    }
     return 0;
 }
 
@@ -2058,24 +2137,9 @@ int lpc_trace_reset(lpc_handle *h)
     h->mp_valid = true;                             // until an iteration does not sum it
     h->m_total = 0;                             // measured record emptied (the first iteration resets the counters)
     h->m_inflight = 0;
-    // the culled-power ledger goes with the measured record (stream-ordered:
-    // behind whatever an earlier trace still runs)
-    h->it_done = 0;
-    if (h->cull_dirty && h->d_cull.p) {
-        HIPCHK(h, hipMemsetAsync(h->d_cull.p, 0, h->d_cull.bytes, h->stream));
-        h->cull_dirty = false;
-    }
-    if (h->bud_dirty) {                             // the power budget likewise
-        if (h->d_bud.p) HIPCHK(h, hipMemsetAsync(h->d_bud.p, 0, h->d_bud.bytes, h->stream));
-        if (h->d_bud_mesh.p) HIPCHK(h, hipMemsetAsync(h->d_bud_mesh.p, 0, h->d_bud_mesh.bytes, h->stream));
-        h->bud_dirty = false;
-    }
-    h->bud_seen = false;
-    if (h->surf_dirty) {                            // and the surface map
-        if (h->d_surf.p) HIPCHK(h, hipMemsetAsync(h->d_surf.p, 0, h->d_surf.bytes, h->stream));
-        h->surf_dirty = false;
-    }
-    return 0;
+    // the ledgers go with the measured record (stream-ordered: behind whatever
+    // an earlier trace still runs)
+    return ledgers_clear(h);
 }
 
 // ---- streamed batches of new rays ------------------------------------------
@@ -2278,12 +2342,12 @@ int lpc_trace_set_min_power(lpc_handle *h, float min_power)
     if (!(min_power >= 0.0f) || !std::isfinite(min_power))
         return set_err(h, LPC_E_ARG, "set_min_power: the cutoff must be finite and >= 0");
     if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
-    if (min_power != h->min_power) {
+    if (min_power != h->led.min_power) {
         // a prediction made under another cutoff is not reused
         h->hist_r.clear();
         h->hist_iter = -1;
     }
-    h->min_power = min_power;           // from the next launched iteration
+    h->led.min_power = min_power;           // from the next launched iteration
     return 0;
 }
 
@@ -2292,14 +2356,14 @@ int lpc_trace_culled(lpc_handle *h, int64_t *count, double *power, int32_t cap, 
     if (!h || !n_iter) return set_err(h, LPC_E_ARG, "null argument");
     if (cap < 0 || (cap > 0 && (!count || !power))) return set_err(h, LPC_E_ARG, "trace_culled: missing buffer");
     RETIF(settle(h));
-    const int64_t n = std::min<int64_t>(h->it_done, kCullSlots);
+    const int64_t n = std::min<int64_t>(h->led.it_done, kCullSlots);
     *n_iter = (int32_t)n;
     const int64_t m = std::min<int64_t>(n, cap);
     for (int64_t i = 0; i < m; ++i) { count[i] = 0; power[i] = 0.0; }
-    if (m > 0 && h->d_cull.p) {
+    if (m > 0 && h->led.cull.buf.p) {
         HIPCHK(h, hipSetDevice(h->device));
         std::vector<CullSlot> v((size_t)m);
-        HIPCHK(h, hipMemcpyAsync(v.data(), h->d_cull.p, (size_t)m * sizeof(CullSlot), hipMemcpyDeviceToHost,
+        HIPCHK(h, hipMemcpyAsync(v.data(), h->led.cull.buf.p, (size_t)m * sizeof(CullSlot), hipMemcpyDeviceToHost,
                                  h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         for (int64_t i = 0; i < m; ++i) { count[i] = (int64_t)v[(size_t)i].count; power[i] = v[(size_t)i].power; }
@@ -2310,7 +2374,7 @@ int lpc_trace_culled(lpc_handle *h, int64_t *count, double *power, int32_t cap, 
 int lpc_trace_set_budget(lpc_handle *h, int on)
 {
     if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
-    h->budget = on != 0;                // from the next launched iteration
+    h->led.budget = on != 0;                // from the next launched iteration
     return 0;
 }
 
@@ -2324,30 +2388,22 @@ int lpc_trace_budget(lpc_handle *h, lpc_budget_iter *per_iter, int32_t iter_cap,
     if ((mesh_power || mesh_count) && mesh_cap < h->scene.K)
         return set_err(h, LPC_E_ARG, "trace_budget: mesh capacity below the scene's mesh count");
     RETIF(settle(h));
-    const int64_t n = h->bud_seen ? std::min<int64_t>(h->it_done, kCullSlots) : 0;
+    const Ledgers &G = h->led;
+    const int64_t n = G.bud_seen ? std::min<int64_t>(G.it_done, kCullSlots) : 0;
     *n_iter = (int32_t)n;
     const int64_t m = std::min<int64_t>(n, iter_cap);
-    const size_t kt = (size_t)h->scene.K * 4;
     if (m > 0) memset(per_iter, 0, (size_t)m * sizeof(lpc_budget_iter));
-    if (mesh_power) memset(mesh_power, 0, kt * sizeof(double));
-    if (mesh_count) memset(mesh_count, 0, kt * sizeof(int64_t));
-    if (!h->bud_dirty) return 0;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (m > 0 && h->d_bud.p)
-        HIPCHK(h, hipMemcpyAsync(per_iter, h->d_bud.p, (size_t)m * sizeof(BudgetRow), hipMemcpyDeviceToHost, h->stream));
-    if (h->d_bud_mesh.p && h->bud_K == h->scene.K && kt > 0) {
-        const char *d = (const char *)h->d_bud_mesh.p;
-        if (mesh_power) HIPCHK(h, hipMemcpyAsync(mesh_power, d, kt * 8, hipMemcpyDeviceToHost, h->stream));
-        if (mesh_count) HIPCHK(h, hipMemcpyAsync(mesh_count, d + 3 * kt * 8, kt * 8, hipMemcpyDeviceToHost, h->stream));
+    if (m > 0 && G.bud.dirty) {         // (waited for with the tables: rows and tables are dirty together)
+        HIPCHK(h, hipSetDevice(h->device));
+        HIPCHK(h, hipMemcpyAsync(per_iter, G.bud.buf.p, (size_t)m * sizeof(BudgetRow), hipMemcpyDeviceToHost, h->stream));
     }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return 0;
+    return staged_read(h, G.bud_mesh, (int64_t)h->scene.K * 4, {mesh_power, mesh_count});
 }
 
 int lpc_trace_set_surface(lpc_handle *h, int on)
 {
     if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
-    h->surface = on != 0;               // from the next launched iteration
+    h->led.surface = on != 0;               // from the next launched iteration
     return 0;
 }
 
@@ -2364,18 +2420,7 @@ int lpc_trace_surface(lpc_handle *h, double *incident, double *deposited, int64_
     if ((incident || deposited || count) && tri_cap < M)
         return set_err(h, LPC_E_ARG, "trace_surface: triangle capacity below the scene's triangle count");
     RETIF(settle(h));
-    const size_t m = (size_t)M;
-    if (incident) memset(incident, 0, m * sizeof(double));
-    if (deposited) memset(deposited, 0, m * sizeof(double));
-    if (count) memset(count, 0, m * sizeof(int64_t));
-    if (!h->surf_dirty || !h->d_surf.p || h->surf_M != h->scene.M || m == 0) return 0;
-    HIPCHK(h, hipSetDevice(h->device));
-    const char *d = (const char *)h->d_surf.p;                  // the trace's table: the first three columns
-    if (incident) HIPCHK(h, hipMemcpyAsync(incident, d, m * 8, hipMemcpyDeviceToHost, h->stream));
-    if (deposited) HIPCHK(h, hipMemcpyAsync(deposited, d + m * 8, m * 8, hipMemcpyDeviceToHost, h->stream));
-    if (count) HIPCHK(h, hipMemcpyAsync(count, d + 2 * m * 8, m * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return 0;
+    return staged_read(h, h->led.surf, M, {incident, deposited, count});
 }
 
 int lpc_shm_comm_open(const char *name, int32_t rank, int32_t world, int32_t create, lpc_shm_comm **out)
@@ -2488,10 +2533,10 @@ struct Pending {
     bool empty = false;         // nothing to do (n_in 0, host-sized)
     int64_t n_bound = 0;        // device-sized: population bound
     double thr = -INFINITY;     // fused: the stop threshold its k_stage_move applied (IterPlan::thr)
-    bool bud = false;           // it ran with the power budget on: its per-mesh staging table ...
-    int bpar = 0;               // ... of this parity joins the trace's when it is collected
-    bool surf = false;          // it ran with the surface map on: its per-triangle staging table likewise
-    int spar = 0;
+    int64_t slot = 0;           // its slot in the trace's ledgers: the iterations collected at its enqueue, one
+                                //   more for a device-sized one (the iteration before it is still uncollected)
+    LedgerSet on;               // the ledgers it ran with: their staging tables of the slot's parity join the
+                                //   trace's when it is collected
     PopState before;            // the population's role before its enqueue (undo of a discarded speculative iteration)
 };
 
@@ -2582,6 +2627,18 @@ struct IterOut {
     bool per_ray() const { return origin4 || dest4 || pow || meas; }
 };
 
+// The ledgers of one enqueued iteration: which are on, the fate records the
+// shading writes for the budget or the map (tri: their seventh array, surface
+// map on, else NULL), and the sum kernels' arguments (off: zeros).
+struct LedgerPlan {
+    LedgerSet on;
+    BudgetRec R = {};
+    int32_t *tri = nullptr;
+    CullSumArgs CS = {};
+    BudgetSumArgs BS = {};
+    SurfaceSumArgs SS = {};
+};
+
 // What the chunks of one enqueued iteration share.
 struct IterPlan {
     int64_t N = 0, C = 0;                   // the population (device-sized: its bound), rays per chunk
@@ -2595,185 +2652,127 @@ struct IterPlan {
     DevAcc *host_acc = nullptr;             // early: the mapped ring slot the counters are published to
     unsigned seq = 0;
     bool want_box = false;                  // fused: the chunks write the children's origin box (d_pbox)
-    bool cut = false;                       // power cutoff: the compaction's CUT instantiations ...
-    CullSumArgs CS;                         // ... and the ledger's arguments (both cull_setup's)
-    bool bud = false;                       // power budget: k_budget_sum runs, with the ledger's arguments ...
-    BudgetSumArgs BS;                       // ... (budget_setup's; BS.R: the fate records, budget or surface map)
-    int32_t *bud_tri = nullptr;             // the records' seventh array (surface map on, else NULL)
-    bool surf = false;                      // surface map: k_surface_sum runs, with ...
-    SurfaceSumArgs SS;                      // ... the map's arguments (surface_setup's)
-    bool rec() const { return bud || surf; }    // the shading's BUD instantiations write the fate records
+    LedgerPlan L;                           // the ledgers it runs with (ledgers_setup)
 };
 
-// Power cutoff: this launch's per-tile culled sums and the iteration's ledger
-// slot (a device-sized iteration is enqueued while the iteration before it is
-// uncollected: the slot after its).  Off: I->CS stays zero.
-static int cull_setup(lpc_handle *h, IterPlan *I)
+// The fate records of one chunk, for the power budget or the surface map: six
+// arrays of ws_rays, and the hit triangle with the map on.
+static int fate_records(lpc_handle *h, LedgerPlan *L)
 {
-    CullSumArgs *CS = &I->CS;
-    memset(CS, 0, sizeof(*CS));
-    I->cut = h->min_power > 0.0f;
-    if (!I->cut) return 0;
-    const int64_t slot = h->it_done + (I->ds ? 1 : 0);
-    if (slot >= kCullSlots)
-        return set_err(h, LPC_E_STATE, "trace: the culled-power ledger holds " + std::to_string(kCullSlots) +
-                                           " iterations");
-    if (!h->d_cull.p) {
-        RETIF(dalloc(h, h->d_cull, (size_t)kCullSlots * sizeof(CullSlot)));
-        HIPCHK(h, hipMemsetAsync(h->d_cull.p, 0, h->d_cull.bytes, h->stream));
-    }
-    const size_t nt_ws = ((size_t)h->ws_rays + LPC_ST_TILE - 1) / LPC_ST_TILE;
-    RETIF(dalloc(h, h->w_cull, nt_ws * (8 + 4) + 64));
-    CS->cp = (const double *)h->w_cull.p;
-    CS->cc = (const uint32_t *)(CS->cp + nt_ws);
-    CS->slot = (CullSlot *)h->d_cull.p + slot;
-    h->cull_dirty = true;
+    const size_t C = (size_t)h->ws_rays;
+    RETIF(dalloc(h, h->led.w_rec, (L->on.surf ? 7 : 6) * C * 4));
+    float *f = (float *)h->led.w_rec.p;
+    L->R.dn = (int32_t *)f; L->R.hit = (int32_t *)(f + C);
+    L->R.pin = f + 2 * C; L->R.p = f + 3 * C; L->R.kr = f + 4 * C; L->R.kt = f + 5 * C;
+    if (L->on.surf) L->tri = (int32_t *)(f + 6 * C);
     return 0;
 }
 
-// Power budget: the chunk's fate records, the iteration's row (the slot rule of
-// cull_setup) and its per-mesh staging table, both zeroed here, before the
-// iteration's first chunk: an iteration that is re-run starts from zero again,
-// and a dropped speculative iteration's sums never reach the trace's table
-// (iter_collect adds a kept iteration's).  Off: I->BS stays zero, but for the
-// records when the surface map (surface_setup) needs them.
-static int budget_setup(lpc_handle *h, IterPlan *I, Pending *P)
+// The ledgers of an iteration about to be enqueued.  It books into slot P->slot:
+// a row of the per-iteration ledgers, and by the slot's parity one of the two
+// staging tables.  Both are zeroed here, before the iteration's first chunk
+// (k_cull_sum instead writes its slot on the first chunk): a re-run iteration
+// starts from zero again, and a dropped speculative iteration's sums never reach
+// the trace's tables (ledgers_commit adds a kept iteration's).  The surface map
+// has no per-iteration rows and runs past kCullSlots iterations.
+static int ledgers_setup(lpc_handle *h, IterPlan *I, Pending *P)
 {
-    BudgetSumArgs *BS = &I->BS;
-    memset(BS, 0, sizeof(*BS));
-    I->bud = h->budget;
-    I->bud_tri = nullptr;
-    if (h->budget || h->surface) {      // the fate records: six arrays, and the triangle with the surface map on
-        const size_t C = (size_t)h->ws_rays;
-        RETIF(dalloc(h, h->w_bud, (h->surface ? 7 : 6) * C * 4));
-        float *f = (float *)h->w_bud.p;
-        BS->R.dn = (int32_t *)f; BS->R.hit = (int32_t *)(f + C);
-        BS->R.pin = f + 2 * C; BS->R.p = f + 3 * C; BS->R.kr = f + 4 * C; BS->R.kt = f + 5 * C;
-        if (h->surface) I->bud_tri = (int32_t *)(f + 6 * C);
-    }
-    if (!I->bud) return 0;
-    const int64_t slot = h->it_done + (I->ds ? 1 : 0);
-    if (slot >= kCullSlots)
-        return set_err(h, LPC_E_STATE, "trace: the power budget holds " + std::to_string(kCullSlots) + " iterations");
-    if (!h->d_bud.p) {
-        RETIF(dalloc(h, h->d_bud, (size_t)kCullSlots * sizeof(BudgetRow)));
-        HIPCHK(h, hipMemsetAsync(h->d_bud.p, 0, h->d_bud.bytes, h->stream));
-    }
-    const int32_t K = h->scene.K;
-    const size_t kt = (size_t)K * 4;
-    if (!h->d_bud_mesh.p || h->bud_K != K) {
-        // (a scene with another mesh count comes with new rays: the ledger was cleared)
-        RETIF(dalloc(h, h->d_bud_mesh, 3 * kt * 16));
-        HIPCHK(h, hipMemsetAsync(h->d_bud_mesh.p, 0, h->d_bud_mesh.bytes, h->stream));
-        h->bud_K = K;
-    }
-    BS->mat_type = (const int32_t *)h->scene.d_mat.p;
-    BS->K = K;
-    BS->row = (BudgetRow *)h->d_bud.p + slot;
+    Ledgers &G = h->led;
+    LedgerPlan &L = I->L = LedgerPlan();
+    const LedgerSet on = P->on = L.on = LedgerSet{G.min_power > 0.0f, G.budget, G.surface};
+    const int64_t slot = P->slot;
     const int par = (int)(slot & 1);
-    double *mp = (double *)h->d_bud_mesh.p;
-    unsigned long long *mc = (unsigned long long *)(mp + 3 * kt);
-    BS->mp = mp + (size_t)(1 + par) * kt;
-    BS->mc = mc + (size_t)(1 + par) * kt;
-    HIPCHK(h, hipMemsetAsync(BS->row, 0, sizeof(BudgetRow), h->stream));
-    HIPCHK(h, hipMemsetAsync(BS->mp, 0, kt * 8, h->stream));
-    HIPCHK(h, hipMemsetAsync(BS->mc, 0, kt * 8, h->stream));
-    h->bud_dirty = true;
-    P->bud = true;
-    P->bpar = par;
-    return 0;
-}
-
-// Power budget: the chunk's records into the iteration's row and staging table.
-static void budget_sum(lpc_handle *h, const IterPlan &I, int64_t nc, const long long *nd)
-{
-    BudgetSumArgs BS = I.BS;
-    BS.n = nc; BS.nd = nd;
-    const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>((nc + 255) / 256, 1024));
-    hipLaunchKernelGGL(k_budget_sum, dim3(nb), dim3(256), 0, h->stream, BS);
-}
-
-// Power budget: a collected iteration's staging table into the trace's.
-static int budget_commit(lpc_handle *h, const Pending &P)
-{
-    if (!P.bud || P.empty || !h->d_bud_mesh.p) return 0;
-    const size_t kt = (size_t)h->bud_K * 4;
-    if (kt == 0) return 0;
-    double *mp = (double *)h->d_bud_mesh.p;
-    unsigned long long *mc = (unsigned long long *)(mp + 3 * kt);
-    const unsigned nb = (unsigned)std::min<size_t>((kt + 255) / 256, 64);
-    hipLaunchKernelGGL(k_budget_commit, dim3(nb), dim3(256), 0, h->stream, mp, mc,
-                       (const double *)(mp + (size_t)(1 + P.bpar) * kt),
-                       (const unsigned long long *)(mc + (size_t)(1 + P.bpar) * kt), (int)kt);
-    HIPCHK(h, hipGetLastError());
-    h->inflight = true;
-    return 0;
-}
-
-// Surface map (after budget_setup, whose records it reads): the per-triangle
-// tables and the iteration's staging table, chosen by the slot's parity and
-// zeroed here, before the iteration's first chunk -- budget_setup's rules.
-// Off: I->SS stays zero.
-static int surface_setup(lpc_handle *h, IterPlan *I, Pending *P)
-{
-    SurfaceSumArgs *SS = &I->SS;
-    memset(SS, 0, sizeof(*SS));
-    I->surf = h->surface;
-    if (!I->surf) return 0;
-    const int32_t M = h->scene.M;
-    const size_t m = (size_t)M;
-    if (!h->d_surf.p || h->surf_M != M) {
-        // (a scene with another triangle count comes with new rays: the tables were cleared)
-        RETIF(dalloc(h, h->d_surf, 9 * m * 8));
-        HIPCHK(h, hipMemsetAsync(h->d_surf.p, 0, h->d_surf.bytes, h->stream));
-        h->surf_M = M;
+    if ((on.cut || on.bud) && slot >= kCullSlots)
+        return set_err(h, LPC_E_STATE, std::string("trace: the ") + (on.cut ? "culled-power ledger" : "power budget") +
+                                           " holds " + std::to_string(kCullSlots) + " iterations");
+    if (on.cut) {                       // this launch's per-tile culled sums and the slot
+        RETIF(ledger_shape(h, G.cull, (size_t)kCullSlots * sizeof(CullSlot)));
+        const size_t nt_ws = ((size_t)h->ws_rays + LPC_ST_TILE - 1) / LPC_ST_TILE;
+        RETIF(dalloc(h, G.w_cull, nt_ws * (8 + 4) + 64));
+        L.CS.cp = (const double *)G.w_cull.p;
+        L.CS.cc = (const uint32_t *)(L.CS.cp + nt_ws);
+        L.CS.slot = G.cull.row<CullSlot>(slot);
+        G.cull.dirty = true;
     }
-    const int64_t slot = h->it_done + (I->ds ? 1 : 0);
-    const int par = (int)(slot & 1);
-    double *st = (double *)h->d_surf.p + (size_t)(1 + par) * 3 * m;
-    SS->R = I->BS.R; SS->tri = I->bud_tri;
-    SS->mat_type = (const int32_t *)h->scene.d_mat.p;
-    SS->K = h->scene.K; SS->M = M;
-    SS->inc = st; SS->dep = st + m; SS->cnt = (unsigned long long *)(st + 2 * m);
-    if (m > 0) HIPCHK(h, hipMemsetAsync(st, 0, 3 * m * 8, h->stream));
-    h->surf_dirty = true;
-    P->surf = true;
-    P->spar = par;
+    if (on.rec()) RETIF(fate_records(h, &L));
+    if (on.bud) {                       // the row, and the per-mesh staging table [K][4]: power, count
+        RETIF(ledger_shape(h, G.bud, (size_t)kCullSlots * sizeof(BudgetRow)));
+        RETIF(staged_shape(h, G.bud_mesh, (int64_t)h->scene.K * 4));
+        double *st = G.bud_mesh.staging(par);
+        L.BS.R = L.R;
+        L.BS.mat_type = (const int32_t *)h->scene.d_mat.p;
+        L.BS.K = h->scene.K;
+        L.BS.row = G.bud.row<BudgetRow>(slot);
+        L.BS.mp = st; L.BS.mc = (unsigned long long *)G.bud_mesh.col(st, 1);
+        HIPCHK(h, hipMemsetAsync(L.BS.row, 0, sizeof(BudgetRow), h->stream));
+        RETIF(staged_zero(h, G.bud_mesh, par));
+        G.bud.dirty = G.bud_mesh.dirty = true;
+    }
+    if (on.surf) {                      // the per-triangle staging table [M]: incident, deposited, count
+        StagedTable &T = G.surf;
+        RETIF(staged_shape(h, T, h->scene.M));
+        double *st = T.staging(par);
+        L.SS.R = L.R; L.SS.tri = L.tri;
+        L.SS.mat_type = (const int32_t *)h->scene.d_mat.p;
+        L.SS.K = h->scene.K; L.SS.M = h->scene.M;
+        L.SS.inc = st; L.SS.dep = T.col(st, 1); L.SS.cnt = (unsigned long long *)T.col(st, 2);
+        RETIF(staged_zero(h, T, par));
+        T.dirty = true;
+    }
     return 0;
 }
 
-// Surface map: the chunk's records into the iteration's staging table.
-static void surface_sum(lpc_handle *h, const IterPlan &I, int64_t nc, const long long *nd)
+// A chunk's sums into the iteration's ledgers: the culled sums of the
+// compaction's tiles (`tile` rays each; off the counters' publication) and the
+// sums over the fate records.  A fused chunk takes both at its end; a plain
+// chunk has its records after the shading and its tiles after k_count.
+enum : unsigned { kSumCulled = 1, kSumRecords = 2 };
+static void ledgers_sum(lpc_handle *h, const IterPlan &I, int64_t base, int64_t nc, int tile, unsigned what)
 {
-    SurfaceSumArgs SS = I.SS;
-    SS.n = nc; SS.nd = nd;
+    const LedgerPlan &L = I.L;
+    if ((what & kSumCulled) && L.on.cut) {
+        CullSumArgs CS = L.CS;
+        CS.first = base == 0 ? 1 : 0;
+        CS.ntiles = (nc + tile - 1) / tile; CS.tile = tile; CS.nd = I.nd();
+        hipLaunchKernelGGL(k_cull_sum, dim3(1), dim3(256), 0, h->stream, CS);
+    }
+    if (!(what & kSumRecords)) return;
     const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>((nc + 255) / 256, 1024));
-    hipLaunchKernelGGL(k_surface_sum, dim3(nb), dim3(256), 0, h->stream, SS);
+    if (L.on.bud) {
+        BudgetSumArgs BS = L.BS;
+        BS.n = nc; BS.nd = I.nd();
+        hipLaunchKernelGGL(k_budget_sum, dim3(nb), dim3(256), 0, h->stream, BS);
+    }
+    if (L.on.surf) {
+        SurfaceSumArgs SS = L.SS;
+        SS.n = nc; SS.nd = I.nd();
+        hipLaunchKernelGGL(k_surface_sum, dim3(nb), dim3(256), 0, h->stream, SS);
+    }
 }
 
-// Surface map: a collected iteration's staging table into the trace's.
-static int surface_commit(lpc_handle *h, const Pending &P)
+// A collected iteration's staging tables into the trace's (the kernels differ:
+// each skips the entries its own count column leaves at zero).
+static int ledgers_commit(lpc_handle *h, const Pending &P)
 {
-    if (!P.surf || P.empty || !h->d_surf.p || h->surf_M == 0) return 0;
-    const size_t m = (size_t)h->surf_M;
-    double *tot = (double *)h->d_surf.p;
-    const double *st = tot + (size_t)(1 + P.spar) * 3 * m;
-    const unsigned nb = (unsigned)std::min<size_t>((m + 255) / 256, 1024);
-    hipLaunchKernelGGL(k_surface_commit, dim3(nb), dim3(256), 0, h->stream, tot, tot + m,
-                       (unsigned long long *)(tot + 2 * m), st, st + m, (const unsigned long long *)(st + 2 * m),
-                       (int)m);
-    HIPCHK(h, hipGetLastError());
-    h->inflight = true;
+    const int par = (int)(P.slot & 1);
+    const StagedTable &B = h->led.bud_mesh, &S = h->led.surf;
+    if (P.on.bud && B.live()) {
+        double *tot = B.total(), *st = B.staging(par);
+        hipLaunchKernelGGL(k_budget_commit, dim3((unsigned)std::min<int64_t>((B.n + 255) / 256, 64)), dim3(256), 0,
+                           h->stream, tot, (unsigned long long *)B.col(tot, 1), (const double *)st,
+                           (const unsigned long long *)B.col(st, 1), (int)B.n);
+        HIPCHK(h, hipGetLastError());
+        h->inflight = true;
+    }
+    if (P.on.surf && S.live()) {
+        double *tot = S.total(), *st = S.staging(par);
+        hipLaunchKernelGGL(k_surface_commit, dim3((unsigned)std::min<int64_t>((S.n + 255) / 256, 1024)), dim3(256), 0,
+                           h->stream, tot, S.col(tot, 1), (unsigned long long *)S.col(tot, 2), (const double *)st,
+                           (const double *)S.col(st, 1), (const unsigned long long *)S.col(st, 2), (int)S.n);
+        HIPCHK(h, hipGetLastError());
+        h->inflight = true;
+    }
     return 0;
-}
-
-// Power cutoff: the chunk's culled sums into the ledger slot, off the counters' publication.
-static void cull_sum(lpc_handle *h, const IterPlan &I, int64_t base, int64_t ntiles, int tile, const long long *nd)
-{
-    CullSumArgs CS = I.CS;
-    CS.first = base == 0 ? 1 : 0;
-    CS.ntiles = ntiles; CS.tile = tile; CS.nd = nd;
-    hipLaunchKernelGGL(k_cull_sum, dim3(1), dim3(256), 0, h->stream, CS);
 }
 
 // One chunk of a traced iteration: shade + staged compaction, two kernels
@@ -2809,12 +2808,12 @@ static int enqueue_fused_chunk(lpc_handle *h, const IterPlan &I, const RaysIn &i
     G.gsum = gs + gt.cur;
     G.tmask = tmask;
     G.tbox = I.want_box ? (uint32_t *)h->w_tbox.p : nullptr;
-    G.cut = h->min_power; G.tcc = (uint32_t *)I.CS.cc; G.tcp = (double *)I.CS.cp;
-    G.bud = I.BS.R; G.bud_tri = I.bud_tri ? 1u : 0u;       // (the records' stride is cst: both are ws_rays)
+    G.cut = h->led.min_power; G.tcc = (uint32_t *)I.L.CS.cc; G.tcp = (double *)I.L.CS.cp;
+    G.bud = I.L.R; G.bud_tri = I.L.tri ? 1u : 0u;       // (the records' stride is cst: both are ws_rays)
     // (this nesting keeps the instantiations in their order in the code object;
     // the power budget's come after the others)
     auto launch_stage = [&](auto bud) {
-        with_bool(I.cut, [&](auto ct) {
+        with_bool(I.L.on.cut, [&](auto ct) {
             with_bool(ds != nullptr, [&](auto dsz) {
                 with_ku(h->scene.K, [&](auto ku) {
                     hipLaunchKernelGGL((k_shade_stage<decltype(ku)::value, decltype(dsz)::value, decltype(ct)::value,
@@ -2824,7 +2823,7 @@ static int enqueue_fused_chunk(lpc_handle *h, const IterPlan &I, const RaysIn &i
             });
         });
     };
-    if (!I.rec()) launch_stage(std::false_type{});
+    if (!I.L.on.rec()) launch_stage(std::false_type{});
     else launch_stage(std::true_type{});
     MoveArgs M;
     M.ntiles = nt_max; M.ngroups = ng;
@@ -2854,9 +2853,7 @@ static int enqueue_fused_chunk(lpc_handle *h, const IterPlan &I, const RaysIn &i
     with_bool(ds != nullptr, [&](auto dsz) {
         hipLaunchKernelGGL(k_stage_move<decltype(dsz)::value>, dim3((unsigned)nt), dim3(LPC_ST_TILE), 0, h->stream, M);
     });
-    if (I.cut) cull_sum(h, I, base, nt_max, LPC_ST_TILE, I.nd());
-    if (I.bud) budget_sum(h, I, nc, I.nd());
-    if (I.surf) surface_sum(h, I, nc, I.nd());
+    ledgers_sum(h, I, base, nc, LPC_ST_TILE, kSumCulled | kSumRecords);
     // k_shade_stage restored what it read, k_stage_move reset the next launch's words
     h->slots = SlotState{/*clean*/ true, h->emitted.max_ray_len, /*misc_clean*/ true};
     HIPCHK(h, hipGetLastError());
@@ -2902,23 +2899,22 @@ static int enqueue_plain_chunk(lpc_handle *h, const IterPlan &I, const IterOut &
     A.mm = (int32_t *)(mf + 4 * mc);
     A.host_acc = I.host_acc;
     A.seq = I.seq;
-    A.cut = h->min_power; A.blk_cc = (uint32_t *)I.CS.cc; A.blk_cp = (double *)I.CS.cp;
-    if (I.rec()) {                      // k_shade with the fate records, and their sums
+    A.cut = h->led.min_power; A.blk_cc = (uint32_t *)I.L.CS.cc; A.blk_cp = (double *)I.L.CS.cp;
+    if (I.L.on.rec()) {                 // k_shade with the fate records, and their sums
         const ShadeArgs SA = shade_args(h, in, nullptr, nc, h->emitted.max_ray_len, h->emitted.ior_env, false);
         with_ku(h->scene.K, [&](auto ku) {
-            hipLaunchKernelGGL(k_shade_bud<decltype(ku)::value>, dim3(grid1(nc)), dim3(256), 0, h->stream, SA, I.BS.R,
-                               I.bud_tri);
+            hipLaunchKernelGGL(k_shade_bud<decltype(ku)::value>, dim3(grid1(nc)), dim3(256), 0, h->stream, SA, I.L.R,
+                               I.L.tri);
         });
         HIPCHK(h, hipGetLastError());
-        if (I.bud) budget_sum(h, I, nc, nullptr);
-        if (I.surf) surface_sum(h, I, nc, nullptr);
+        ledgers_sum(h, I, base, nc, 1024, kSumRecords);
     } else {
         RETIF(run_shade(h, in, nullptr, nc, h->emitted.max_ray_len, h->emitted.ior_env, false));
     }
-    with_bool(I.cut, [&](auto ct) {
+    with_bool(I.L.on.cut, [&](auto ct) {
         hipLaunchKernelGGL(k_count<decltype(ct)::value>, dim3((unsigned)A.nb), dim3(256), 0, h->stream, A);
     });
-    if (I.cut) cull_sum(h, I, base, A.nb, 1024, nullptr);
+    ledgers_sum(h, I, base, nc, 1024, kSumCulled);
     if (O.X) {
         const double hx = h->knobs.host_prof ? host_us() : 0.0;
         RETIF(export_chunk(h, in, o, nc, base, I.N, *O.X));
@@ -2926,7 +2922,7 @@ static int enqueue_plain_chunk(lpc_handle *h, const IterPlan &I, const IterOut &
     }
     if (O.per_ray()) RETIF(copy_per_ray(h, O, in, o, base, nc));
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, h->stream, A);
-    with_bool(I.cut, [&](auto ct) {
+    with_bool(I.L.on.cut, [&](auto ct) {
         hipLaunchKernelGGL(k_scatter<decltype(ct)::value>, dim3((unsigned)A.nb), dim3(256), 0, h->stream, A);
     });
     HIPCHK(h, hipGetLastError());
@@ -2942,7 +2938,8 @@ static int iter_enqueue(lpc_handle *h, const IterOut &O, const DevSize *ds, doub
 {
     *P = Pending();
     P->before = h->pop;
-    if (h->budget) h->bud_seen = true;  // (an empty population too: its row is zeros)
+    P->slot = h->led.it_done + (ds ? 1 : 0);
+    if (h->led.budget) h->led.bud_seen = true;  // (an empty population too: its row is zeros)
     IterPlan I;
     const int64_t N = I.N = ds ? ds->bound : h->pop.n;
     P->n_in = ds ? -1 : N;
@@ -2958,9 +2955,7 @@ static int iter_enqueue(lpc_handle *h, const IterOut &O, const DevSize *ds, doub
     if (!ds) RETIF(pop_reserve(h, h->T, N));
     // measured rows: the iterations still in flight may append up to their populations
     RETIF(ensure_measured(h, h->m_total + h->m_inflight + N));
-    RETIF(cull_setup(h, &I));
-    RETIF(budget_setup(h, &I, P));
-    RETIF(surface_setup(h, &I, P));
+    RETIF(ledgers_setup(h, &I, P));
     if (h->knobs.host_prof)
         fprintf(stderr, "[lpc host]   buffers %.1f us (m_total %lld inflight %lld m_cap %lld)\n", host_us() - hp0,
                 (long long)h->m_total, (long long)h->m_inflight, (long long)h->m_cap);
@@ -3033,10 +3028,9 @@ static int iter_collect(lpc_handle *h, const Pending &P, float *out_next_pow, lp
     memset(&S, 0, sizeof(S));
     S.n_in = P.n_in;
     S.power_nonneg = 1;
-    ++h->it_done;                       // the ledger's slot count (an empty iteration's slot stays zero)
+    ++h->led.it_done;                   // the ledgers' slot count (an empty iteration's slot stays zero)
     if (P.empty) { if (st) *st = S; return 0; }
-    RETIF(budget_commit(h, P));
-    RETIF(surface_commit(h, P));
+    RETIF(ledgers_commit(h, P));
     DevAcc acc;
     const double t_wait = h->knobs.host_prof ? host_us() : 0.0;
     if (P.early) {

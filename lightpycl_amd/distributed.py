@@ -25,6 +25,8 @@ import weakref
 
 import numpy as np
 
+from .ledgers import read_ledgers
+
 
 class TorchComm:
     """All-reduce of small float64 vectors over torch.distributed (RCCL on GPU,
@@ -238,52 +240,9 @@ class ShardedTrace:
             _, mesh_pow = self.engine.measured()
             mesh_pow = self._sum(np.asarray(mesh_pow, dtype=np.float64))
         out = dict(bounces=bounces, iterations=iters, global_counts=counts, mesh_power=mesh_pow)
-        if getattr(self.engine, "min_power", 0.0) > 0.0:
-            # the culled-power ledger (Engine.set_min_power, the same cutoff on every
-            # rank) summed over the ranks at the trace's end, through this object's
-            # comm (every rank ran the same number of iterations); the library's
-            # per-iteration hook and its payload are untouched
-            cc, cp = self.engine.culled()
-            k = len(cc)
-            tot = self._sum(np.concatenate((np.asarray(cc, np.float64), np.asarray(cp, np.float64))))
-            out["culled_counts"] = [int(v) for v in tot[:k]]
-            out["culled_power"] = [float(v) for v in tot[k:2 * k]]
-        if getattr(self.engine, "budget_on", False):
-            # the power budget (Engine.set_budget, on every rank alike) summed over
-            # the ranks in the same way: `iters` rows of 13 and the (K, 4) tables,
-            # sizes that no rank's data changes (counts are exact in float64)
-            from . import _lib
-            from .iterative_tracer import budget_dict
-            b = self.engine.budget()
-            names = _lib.BUDGET_SUMS + _lib.BUDGET_COUNTS
-            rows = np.zeros((len(names), iters), np.float64)
-            for j, name in enumerate(names):
-                v = np.asarray(b[name], np.float64)[:iters]
-                rows[j, :len(v)] = v
-            kk = b["mesh_power"].size
-            tot = self._sum(np.concatenate((rows.ravel(), b["mesh_power"].ravel(),
-                                            b["mesh_count"].astype(np.float64).ravel())))
-            rows = tot[:rows.size].reshape(len(names), iters)
-            g = {name: (rows[j] if name in _lib.BUDGET_SUMS else np.rint(rows[j]).astype(np.int64))
-                 for j, name in enumerate(names)}
-            g["mesh_power"] = tot[rows.size:rows.size + kk].reshape(-1, 4)
-            g["mesh_count"] = np.rint(tot[rows.size + kk:]).astype(np.int64).reshape(-1, 4)
-            out["power_budget"] = budget_dict(g, out.get("culled_counts", ()), out.get("culled_power", ()))
-        if getattr(self.engine, "surface_on", False):
-            # the surface map (Engine.set_surface, on every rank alike) summed over
-            # the ranks with the same comm: three tables of the scene's triangle
-            # count, a size that no rank's data changes, in pieces of at most
-            # SURFACE_PIECE values (a comm's payload is an int32 count of float64,
-            # and a piece keeps its buffers small); counts are exact in float64
-            s = self.engine.surface()
-            m = len(s["count"])
-            flat = np.concatenate((np.asarray(s["incident"], np.float64), np.asarray(s["deposited"], np.float64),
-                                   np.asarray(s["count"], np.float64)))
-            tot = np.empty_like(flat)
-            for lo in range(0, len(flat), SURFACE_PIECE):
-                tot[lo:lo + SURFACE_PIECE] = self._sum(flat[lo:lo + SURFACE_PIECE])
-            out["surface"] = {"incident": tot[:m].copy(), "deposited": tot[m:2 * m].copy(),
-                              "count": np.rint(tot[2 * m:]).astype(np.int64)}
+        # the ledgers that are on (on every rank alike) summed over the ranks through this
+        # object's comm; the library's per-iteration hook and its payload are untouched
+        out.update(read_ledgers(self.engine, reduce=self._sum, iterations=iters, piece=SURFACE_PIECE))
         if hist is not None:
             limits, points = hist
             H, xe, ye = self.engine.project_hist(None, None, limits, points)[:3]

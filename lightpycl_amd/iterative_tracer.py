@@ -39,6 +39,7 @@ import numpy as np
 
 from . import _lib
 from .engine import Engine, _same_digest, array_digest, flatten_meshes, select_device
+from .ledgers import budget_dict, read_ledgers, surface_dict, triangle_areas  # noqa: F401 (re-exported)
 
 
 def f32_sorted_sum(a):
@@ -53,104 +54,6 @@ def f32_sorted_sum(a):
     out = ctypes.c_float(0.0)
     _lib.check(_lib.load().lpc_host_seq_sum_f32(flat.ctypes.data_as(ctypes.c_void_p), flat.size, ctypes.byref(out)))
     return np.float32(out.value)
-
-
-def triangle_areas(mesh):
-    """Areas of a mesh's triangles in its own triangle order, ``0.5 |E1 x E2|``
-    in float64 from the mesh's vertices as they are held on the host (not the
-    float32 rows of the upload)."""
-    V, T = getattr(mesh, "vertices", None), getattr(mesh, "triangles", None)
-    try:
-        V = np.asarray(V, np.float64)
-        T = np.asarray(T)
-        ok = V.ndim == 2 and V.shape[1] >= 3 and T.ndim == 2 and T.shape[1] == 3 and T.dtype.kind in "iu"
-    except Exception:
-        ok = False
-    if ok:
-        a, b, c = (V[T[:, k], :3] for k in range(3))
-    else:                                       # general vertex containers: the reference's tribuf() lists
-        tb = mesh.tribuf()
-        a, b, c = (np.asarray(tb[k], np.float64).reshape(-1, 4)[:, :3] for k in range(3))
-    return 0.5 * np.linalg.norm(np.cross(b - a, c - a), axis=1)
-
-
-def surface_dict(s, meshes):
-    """The surface map as the tracer returns it, from ``Engine.surface()`` (or
-    the ranks' sum of it) and the traced meshes.
-
-    ``meshes``: per mesh, in the order of the trace's ``meshes``, a dict of
-    arrays in that mesh's own triangle order: ``incident`` (float64: the power of
-    every ray whose nearest hit is the triangle), ``deposited`` (float64: what
-    stayed there -- the whole ray on a terminator or measure mesh, else the ray
-    less its kept children: ``(1 - R) p`` on a mirror, the Fresnel split's
-    float32 residue on a refractive surface), ``count`` (int64 hits), ``area``
-    (:func:`triangle_areas`), ``irradiance`` = deposited / area and
-    ``incident_irradiance`` = incident / area (a zero-area sliver gives inf or
-    nan: it is not hidden), and ``offset``, the mesh's first triangle in the flat
-    arrays.  ``incident``, ``deposited``, ``count``: the flat arrays over all
-    triangles, the order of the scene upload (the reference's ``isect_idx``).
-    Per mesh, ``deposited`` sums to the power budget's absorbed + terminated +
-    measured of that mesh."""
-    inc, dep = np.asarray(s["incident"], np.float64), np.asarray(s["deposited"], np.float64)
-    cnt = np.asarray(s["count"], np.int64)
-    out = {"incident": inc, "deposited": dep, "count": cnt, "meshes": [], "offsets": []}
-    lo = 0
-    for m in meshes:
-        area = triangle_areas(m)
-        hi = lo + len(area)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            out["meshes"].append({"offset": lo, "incident": inc[lo:hi], "deposited": dep[lo:hi], "count": cnt[lo:hi],
-                                  "area": area, "irradiance": dep[lo:hi] / area,
-                                  "incident_irradiance": inc[lo:hi] / area})
-        out["offsets"].append(lo)
-        lo = hi
-    if lo != len(cnt):
-        raise ValueError(f"surface map: the meshes hold {lo} triangles, the scene {len(cnt)}")
-    return out
-
-
-def budget_dict(b, culled_counts=(), culled_power=()):
-    """The power budget as the tracer returns it, from ``Engine.budget()`` and the
-    culled-power ledger of the same trace (empty: no cutoff).
-
-    Per iteration (arrays over the trace's iterations): ``power_in`` and the six
-    float64 sums ``dissipated`` (Beer-Lambert loss inside a medium), ``escaped``
-    (no hit within max_ray_len), ``terminated`` (terminator surfaces),
-    ``measured`` (measure surfaces), ``absorbed`` (what every other hit did not
-    hand to its children: (1 - R) p on a mirror, the whole ray on a type-4 or
-    unknown surface and on the NaN-TIR path, the float32 residue of the Fresnel
-    split on a refractive surface) and ``kept`` (the children's power before
-    any cutoff), with the exact counts ``n_in``, ``n_dissipated``, ``n_escaped``,
-    ``n_terminated``, ``n_measured``, ``n_absorbed``; ``culled`` and ``n_culled``
-    from the cutoff's ledger (zeros without one).
-
-    ``mesh``: ``{category: float64[K]}`` and ``mesh_count``: ``{category:
-    int64[K]}`` for dissipated (the medium's mesh), absorbed, terminated and
-    measured (the hit mesh), summed over the trace.
-
-    ``left``: the last iteration's kept power minus its culled power, the power
-    of the population the stop rule left untraced.  ``closure``: the residue of
-    the whole-trace identity, ``power_in[0]`` minus every iteration's
-    dissipated, escaped, terminated, measured, absorbed and culled power minus
-    ``left``: float64 rounding of the sums when the ledger is whole."""
-    import math
-    from . import _lib
-    n = len(b["n_in"])
-    out = {k: np.asarray(b[k]) for k in _lib.BUDGET_SUMS + _lib.BUDGET_COUNTS}
-    cp = np.zeros(n, np.float64)
-    cc = np.zeros(n, np.int64)
-    m = min(n, len(culled_power))
-    cp[:m] = np.asarray(culled_power, np.float64)[:m]
-    cc[:m] = np.asarray(culled_counts, np.int64)[:m]
-    out["culled"], out["n_culled"] = cp, cc
-    out["mesh"] = {k: np.asarray(b["mesh_power"])[:, j].copy() for j, k in enumerate(_lib.BUDGET_MESH)}
-    out["mesh_count"] = {k: np.asarray(b["mesh_count"])[:, j].copy() for j, k in enumerate(_lib.BUDGET_MESH)}
-    left = float(out["kept"][-1] - cp[-1]) if n else 0.0
-    spent = [float(v) for k in ("dissipated", "escaped", "terminated", "measured", "absorbed", "culled")
-             for v in out[k]]
-    out["left"] = left
-    out["closure"] = math.fsum([float(out["power_in"][0])] + [-v for v in spent] + [-left]) if n else 0.0
-    return out
 
 
 # the tracer's helper thread (created with the module, started on first use)
@@ -373,9 +276,7 @@ class CL_Tracer:
                     break
             ph["loop"] = clk() - t_ph
             t_ph = clk()
-            self._read_culled()
-            self._read_budget()
-            self._read_surface()
+            self._read_ledgers()
         finally:
             self.engine.sync()                  # the exported results arrays are complete
         ph["sync"] = clk() - t_ph
@@ -383,29 +284,15 @@ class CL_Tracer:
         self.sim_time = time.time() - t0
         return self.results
 
-    def _read_culled(self):
-        """The trace's culled-power ledger (read only with a cutoff set: the
-        reader waits for the stream)."""
+    def _read_ledgers(self):
+        """The trace's ledgers (:func:`read_ledgers`): the culled ledger cut to
+        the trace's iterations (zeros without a cutoff), the map per mesh."""
         n = len(self.iteration_counts)
-        if self.engine.min_power > 0.0:
-            cc, cp = self.engine.culled()
-            self.culled_counts = [int(c) for c in cc[:n]]
-            self.culled_power = [float(v) for v in cp[:n]]
-        else:
-            self.culled_counts, self.culled_power = [0] * n, [0.0] * n
-
-    def _read_budget(self):
-        """The trace's power budget (read only with the ledger on: the reader
-        waits for the stream)."""
-        self._budget = None
-        if self.engine.budget_on:
-            self._budget = budget_dict(self.engine.budget(), self.culled_counts, self.culled_power)
-
-    def _read_surface(self):
-        """The trace's surface map (read only with the map on, as the budget)."""
-        self._surface = None
-        if self.engine.surface_on:
-            self._surface = surface_dict(self.engine.surface(), self.meshes)
+        led = read_ledgers(self.engine)
+        self.culled_counts = led["culled_counts"][:n] if "culled_counts" in led else [0] * n
+        self.culled_power = led["culled_power"][:n] if "culled_power" in led else [0.0] * n
+        self._budget = led.get("power_budget")
+        self._surface = surface_dict(led["surface"], self.meshes) if "surface" in led else None
 
     def surface_power(self):
         """The surface map of the last trace (``surface_map=True``), see
@@ -472,9 +359,7 @@ class CL_Tracer:
                           f"kept, {100.0 * self.power_left[-1]:.4f} % power left")
             ph["loop"] = clk() - t_ph
             t_ph = clk()
-            self._read_culled()
-            self._read_budget()
-            self._read_surface()
+            self._read_ledgers()
         finally:
             self.engine.sync()
         ph["sync"] = clk() - t_ph

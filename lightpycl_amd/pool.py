@@ -23,6 +23,7 @@ import threading
 import numpy as np
 
 from .engine import Engine
+from .ledgers import read_ledgers
 
 # Walk grid of engines that trace side by side: 16 384 single-wave blocks ran the
 # headline 2.4 % faster than the default 65 536 with three in flight, and one
@@ -78,15 +79,7 @@ class TracePool:
                "measured_count": int(count), "mesh_power": np.asarray(mesh_power, np.float64)}
         if measured:
             out["measured"] = e.fetch_measured()
-        if min_ray_power:
-            cc, cp = e.culled()
-            out["culled_counts"] = [int(c) for c in cc]
-            out["culled_power"] = [float(v) for v in cp]
-        if power_budget:
-            from .iterative_tracer import budget_dict
-            out["power_budget"] = budget_dict(e.budget(), out.get("culled_counts", ()), out.get("culled_power", ()))
-        if surface_map:
-            out["surface"] = e.surface()
+        out.update(read_ledgers(e))
         return out
 
     def submit(self, origin, direction, power, max_ray_len=1e3, ior_env=1.0, iterations=16, tau=0.99,

@@ -257,6 +257,44 @@ def test_paths(oracle_mod, checker, monkeypatch, name, path):
         e.close()
 
 
+def test_all_ledgers_chunked(oracle_mod, checker):
+    """The cutoff, the budget and the map on one handle, several chunks per
+    iteration, three traces (the later ones on the first's speculation history):
+    the three ledgers share one slot per iteration, and each equals its helper's
+    with equal exact parts in every trace."""
+    from lightpycl_amd.engine import Engine
+    from lightpycl_amd.iterative_tracer import budget_dict
+    sc, (o, d, p), cut, ref = _case(oracle_mod, checker, "eye", 1e-6)
+    assert sum(len(c) for c in ref["budget"]["culled"]) > 0, "the case must cull"
+    thr = _thr(sc, p)
+    e = Engine(0)
+    try:
+        e.upload_meshes(sc.meshes)
+        e.set_chunk(1000)
+        assert max(ref["counts"]) > 1000
+        e.set_min_power(cut)
+        e.set_budget(True)
+        e.set_surface(True)
+        e.set_rays(o, d, p, sc.max_ray_len, sc.ior_env)
+        first = None
+        for rep in range(3):
+            stats, _, _ = _engine_trace(e, sc, thr)
+            what = f"all ledgers, trace {rep}"
+            assert [int(st.n_in) for st in stats] == ref["counts"]
+            s, (cc, cp) = e.surface(), e.culled()
+            b = budget_dict(e.budget(), cc, cp)
+            surface_ref.assert_surface(s, ref, what)
+            budget_ref.assert_budget(b, ref["budget"], what)
+            cutoff_ref.assert_ledger(cc, cp, ref["budget"]["culled"], what)
+            assert [int(c) for c in b["n_culled"]] == [int(c) for c in cc]
+            exact = (s["count"].tolist(), {k: np.asarray(b[k]).tolist() for k in budget_ref.COUNTS},
+                     {k: np.asarray(b["mesh_count"][k]).tolist() for k in budget_ref.MESH_CATS}, cc.tolist())
+            assert first is None or exact == first, what
+            first = exact if first is None else first
+    finally:
+        e.close()
+
+
 def test_device_source(oracle_mod, checker):
     """An on_device=True source (lpc_trace_set_rays_dev)."""
     from lightpycl_amd import light_source as lsrc

@@ -142,3 +142,99 @@ def test_surface_dict_on_the_host():
     assert m1["irradiance"][0] == 2.0 * 64 / 0.375 and m1["incident_irradiance"][2] == 66 / 0.375
     with pytest.raises(ValueError):
         surface_dict(dict(incident=np.zeros(3), deposited=np.zeros(3), count=np.zeros(3, np.int64)), meshes)
+
+
+class _StubEngine:
+    """An engine's ledger readers over fixed arrays (one rank of a sharded trace)."""
+
+    def __init__(self, seed, iters=3, K=2, M=7, min_power=1e-6, budget_on=True, surface_on=True):
+        from lightpycl_amd import _lib
+        rng = np.random.default_rng(seed)
+        self.min_power, self.budget_on, self.surface_on = min_power, budget_on, surface_on
+        self.reads = []
+        self._culled = (rng.integers(0, 50, iters), rng.random(iters))
+        self._budget = {k: rng.random(iters) for k in _lib.BUDGET_SUMS}
+        self._budget.update({k: rng.integers(0, 1000, iters) for k in _lib.BUDGET_COUNTS})
+        self._budget.update(mesh_power=rng.random((K, 4)), mesh_count=rng.integers(0, 1000, (K, 4)))
+        self._surface = dict(incident=rng.random(M), deposited=rng.random(M), count=rng.integers(0, 9, M))
+
+    def culled(self):
+        self.reads.append("culled")
+        return self._culled
+
+    def budget(self):
+        self.reads.append("budget")
+        return self._budget
+
+    def surface(self):
+        self.reads.append("surface")
+        return self._surface
+
+
+def _same(a, b, what=""):
+    if isinstance(a, dict):
+        assert isinstance(b, dict) and list(a) == list(b), (what, list(a), list(b))
+        for k in a:
+            _same(a[k], b[k], f"{what}/{k}")
+    elif isinstance(a, np.ndarray):
+        assert isinstance(b, np.ndarray) and a.dtype == b.dtype and np.array_equal(a, b), what
+    else:
+        assert type(a) is type(b) and a == b, (what, a, b)
+
+
+def test_read_ledgers_on_the_host():
+    """read_ledgers returns only what is on; with a summing ``reduce`` over two
+    stub ranks it equals the dicts built from the element-wise sums (counts as
+    int64), every rank exchanging vectors of the same sizes in the same order,
+    the map's tables in pieces."""
+    from lightpycl_amd import _lib
+    from lightpycl_amd.ledgers import budget_dict, read_ledgers
+    # one engine, no reduce: the readers' own values, and only those that are on
+    e = _StubEngine(1)
+    got = read_ledgers(e)
+    assert list(got) == ["culled_counts", "culled_power", "power_budget", "surface"]
+    assert e.reads == ["culled", "budget", "surface"]
+    assert got["culled_counts"] == [int(v) for v in e._culled[0]] and all(type(v) is int for v in got["culled_counts"])
+    assert got["culled_power"] == [float(v) for v in e._culled[1]]
+    _same(got["power_budget"], budget_dict(e._budget, *e._culled), "budget")
+    assert got["surface"] is e._surface
+    off = _StubEngine(1, min_power=0.0, budget_on=False, surface_on=False)
+    assert read_ledgers(off) == {} and off.reads == []
+    only = _StubEngine(1, min_power=0.0, surface_on=False)
+    got = read_ledgers(only)
+    assert list(got) == ["power_budget"] and only.reads == ["budget"]
+    assert not got["power_budget"]["n_culled"].any() and not got["power_budget"]["culled"].any()
+    assert read_ledgers(object()) == {}             # an engine without the switches has no ledgers
+    # two ranks: rank 1's vectors are recorded, rank 0's reduce adds them in order
+    iters, piece = 3, 5
+    r0, r1 = _StubEngine(2), _StubEngine(3)
+    sent = []
+
+    def record(v):
+        assert v.dtype == np.float64 and v.ndim == 1
+        sent.append(v.copy())
+        return v
+
+    read_ledgers(r1, reduce=record, iterations=iters, piece=piece)
+    M, K = 7, 2
+    assert [len(v) for v in sent] == [2 * iters, 13 * iters + 8 * K] + [5, 5, 5, 5, 1], [len(v) for v in sent]
+    pending = list(sent)
+
+    def add(v):
+        w = pending.pop(0)
+        assert v.dtype == np.float64 and v.shape == w.shape
+        return v + w
+
+    got = read_ledgers(r0, reduce=add, iterations=iters, piece=piece)
+    assert not pending and 3 * M > piece
+    cc = r0._culled[0] + r1._culled[0]
+    cp = r0._culled[1] + r1._culled[1]
+    b = {k: r0._budget[k] + r1._budget[k] for k in r0._budget}
+    s = {k: r0._surface[k] + r1._surface[k] for k in _lib.SURFACE_COLUMNS}
+    assert got["culled_counts"] == [int(v) for v in cc] and got["culled_power"] == [float(v) for v in cp]
+    _same(got["power_budget"], budget_dict(b, cc, cp), "summed budget")
+    for k in _lib.BUDGET_COUNTS + ("n_culled",):
+        assert got["power_budget"][k].dtype == np.int64
+    assert all(v.dtype == np.int64 for v in got["power_budget"]["mesh_count"].values())
+    _same(got["surface"], s, "summed surface")
+    assert got["surface"]["count"].dtype == np.int64 and got["surface"]["incident"].dtype == np.float64
