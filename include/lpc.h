@@ -508,6 +508,72 @@ int lpc_trace_set_surface(lpc_handle *h, int on);
 int lpc_trace_surface(lpc_handle *h, double *incident, double *deposited, int64_t *count, int64_t tri_cap,
                       int64_t *tri_count);
 
+/* ---- volume map ----------------------------------------------------------- */
+/* Opt-in (default off: every result keeps its bits and the kernels launched are
+ * the ones launched without it).  Per voxel of a grid, where the power budget's
+ * `dissipated` term -- the Beer-Lambert loss inside an absorbing medium -- lands.
+ *
+ * Grid.  An axis-aligned box: lo[3], hi[3] float64, lo < hi per axis, all finite;
+ * dims[3] = (nx, ny, nz), each in 1..1024, V = nx ny nz <= 2^27.  Voxel (ix, iy,
+ * iz) has linear index (ix ny + iy) nz + iz.  Voxel edges are lo + k (hi - lo) / n
+ * per axis, in float64.
+ *
+ * Which rays.  A traced ray is booked when its fate record has dn >= 0: the
+ * shading took the dissipation branch (.cl:385-394; the power budget's own test),
+ * on every iteration and every trace path.  Such rays are exactly the rays of the
+ * budget's n_dissipated.
+ *
+ * Per-ray terms, in float64 formed from the float32 values the shading read and
+ * wrote:
+ *   O   the ray's origin as traced
+ *   E   the dest the shading computed (the value its ray_len is measured from)
+ *   D   (double)pin - (double)p                 the budget's dissipated term of the ray
+ *   a   (double)diss[dn] * |E - O|              |.| computed in float64
+ *
+ * How the power is spread.  Along X(s) = O + s (E - O), s in [0,1], the absorbed
+ * fraction up to s is
+ *   W(s) = expm1(-a s) / expm1(-a)   a > 0
+ *   W(s) = s                         a == 0
+ * and voxel v receives D (W(s_out) - W(s_in)) for the interval of s over which
+ * X(s) lies in v.  The part of [0,1] outside the box goes to one scalar,
+ * `outside`.  Intervals of zero length book nothing.  A ray that lies in a voxel
+ * face may book to either neighbour.  (expm1, not 1 - exp: a may be 1e-6 times a
+ * tiny length, where the latter loses every digit, and in the thousands, where
+ * exp(-a) underflows and the form above stays correct.)
+ *
+ * Degenerate cases.  E == O: the whole D goes to O's voxel, or to `outside` when
+ * O is outside the box.  A non-finite O, E or a: the whole D goes to `outside`.
+ * A NaN D propagates into what it touches.
+ *
+ * Outputs.  deposited[V] float64; outside float64; segments int64, exact: the
+ * number of booked rays, the budget's sum of n_dissipated.  Up to float64
+ * summation, sum(deposited) + outside is the budget's `dissipated` summed over
+ * meshes and iterations.  The sums are added with atomics and may differ in their
+ * last bits from run to run. */
+/* Entries of the direct-mapped table in which a block of k_volume_sum merges its
+ * adds (keyed by voxel % entries; tests build colliding voxels from it). */
+#define LPC_VOLUME_LDS_ENTRIES 1024
+/* lo3 == NULL: off.  Holds until changed, from the next launched iteration.  A grid that
+ * differs from the one the current trace booked into discards what was booked.
+ * LPC_E_ARG: non-finite or lo >= hi, a dim outside 1..1024, V > 2^27.  Applies to
+ * every trace path; independent of the power budget and the surface map. */
+int lpc_trace_set_volume(lpc_handle *h, const double *lo3, const double *hi3, const int32_t *dims3);
+/* The map of the current trace, summed over its iterations, on the grid last set
+ * (it stays readable after the map is switched off).  dims3 always written (zeros
+ * when never set).  deposited: V entries; cap < V with it given: LPC_E_ARG, nothing
+ * written.  outside, segments: may be NULL.  Zeros for a trace that ran with the map
+ * off.  Cleared wherever the measured record is.  Waits for the stream. */
+int lpc_trace_volume(lpc_handle *h, double *deposited, int64_t cap, int32_t *dims3,
+                     double *outside, int64_t *segments);
+/* The walk of one segment on the host, by the routine the device runs (lpc_math.hpp
+ * volume_begin / volume_step): the intervals in walk order, idx[i] the voxel or -1
+ * for `outside`, share[i] its power.  *n: the intervals the segment has; the first
+ * min(*n, cap) are written.  No device.  LPC_E_ARG: a grid lpc_trace_set_volume
+ * refuses, a null argument. */
+int lpc_volume_segment_host(const double *lo3, const double *hi3, const int32_t *dims3, const double *O3,
+                            const double *E3, double a, double D, int64_t *idx, double *share, int64_t cap,
+                            int64_t *n);
+
 /* ---- diagnostics ---------------------------------------------------------- */
 /* The device's own conservative-filter code on n (ray, record) pairs, host
  * arrays: origin3/dir3 (n,3), rec5 (n,5) = centre xyz, negB, negA (filter_record /

@@ -33,6 +33,9 @@ BUDGET_COUNTS = ("n_in", "n_dissipated", "n_escaped", "n_terminated", "n_measure
 BUDGET_MESH = ("dissipated", "absorbed", "terminated", "measured")       # the per-mesh table's columns
 SURFACE_COLUMNS = ("incident", "deposited", "count")                     # the surface map's per-triangle columns
 SURFACE_LDS_ENTRIES = 1024      # include/lpc.h LPC_SURFACE_LDS_ENTRIES (k_surface_sum's block table)
+VOLUME_LDS_ENTRIES = 1024       # include/lpc.h LPC_VOLUME_LDS_ENTRIES (k_volume_sum's block table)
+VOLUME_MAX_DIM = 1024           # a grid's dims lie in 1..VOLUME_MAX_DIM, its voxels number at most
+VOLUME_MAX_VOXELS = 1 << 27     #   VOLUME_MAX_VOXELS (lpc_trace_set_volume)
 
 
 class BudgetIter(ctypes.Structure):
@@ -133,6 +136,9 @@ _PROTOS = {
     "lpc_trace_budget": [_P, _P, _I32, _P, _P, _P, _I32],
     "lpc_trace_set_surface": [_P, _INT],
     "lpc_trace_surface": [_P, _P, _P, _P, _I64, _P],
+    "lpc_trace_set_volume": [_P, _P, _P, _P],
+    "lpc_trace_volume": [_P, _P, _I64, _P, _P, _P],
+    "lpc_volume_segment_host": [_P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double, _P, _P, _I64, _P],
 }
 
 # lpc_allreduce_fn (include/lpc.h): int (*)(void *ctx, double *vals, int32_t n)

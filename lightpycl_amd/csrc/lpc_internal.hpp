@@ -189,6 +189,11 @@ struct BudgetRec {                    // [chunk rays] each (SoA)
 // only while their argument block keeps its size (a larger block changed the
 // device-sized instantiations).  The seven arrays are one allocation at one
 // stride, so k_shade_stage finds the seventh from a flag (StageArgs::bud_tri).
+// With the volume map on the record gains the shading's dest as arrays eight to
+// ten (x, y, z) behind the seventh, at the same stride; the positions are fixed
+// whether or not the seventh is written.  bud_tri is the mask of what exists.
+#define LPC_REC_TRI 1u                    // bud_tri bit: the hit triangle (array 6)
+#define LPC_REC_DEST 2u                   // bud_tri bit: dest (arrays 7, 8, 9)
 #define LPC_BUD_SUMS 7                    // power_in, dissipated, escaped, terminated, measured, absorbed, kept
 #define LPC_BUD_CNTS 6                    // n_in, n_dissipated, n_escaped, n_terminated, n_measured, n_absorbed
 #define LPC_BUD_LDS_MESHES 64             // meshes whose [4] table rows a block keeps in LDS (more: global atomics)
@@ -221,6 +226,27 @@ struct SurfaceSumArgs {
     int32_t K, M;                     // meshes, triangles
     double *inc, *dep;                // [M] staging columns of the iteration (zeroed before its first chunk)
     unsigned long long *cnt;          // [M]
+};
+
+// The volume map (lpc_trace_volume): k_volume_sum walks
+// every dissipating record's segment (origin from the chunk's rays, dest from
+// the record) through the voxel grid into the iteration's staging table,
+// k_volume_commit adds a collected iteration's staging table to the trace's.
+// A table is V + 2 float64 entries: the voxels, `outside`, and the segment
+// count (an integer, exact in float64 below 2^53).
+#define LPC_VOL_LDS 1024                  // entries of a block's direct-mapped LDS table (lpc.h: LPC_VOLUME_LDS_ENTRIES)
+struct VolumeSumArgs {
+    const int32_t *dn;                // the records' dn, pin, p
+    const float *pin, *p;
+    const float *ex, *ey, *ez;        // the records' dest
+    const float *ox, *oy, *oz;        // the chunk's rays as the shading read them
+    const float *diss;                // per mesh
+    int64_t n;                        // records of the launch (device-sized: its bound)
+    const long long *nd;              // device-sized launch: the records (NULL: n)
+    int32_t K;
+    lpc::VolumeGrid G;
+    int64_t V;                        // voxels
+    double *dep;                      // [V + 2] staging table of the iteration (zeroed before its first chunk)
 };
 
 struct CompactArgs {
@@ -281,7 +307,7 @@ struct StageArgs {
                                       //   max xyz), or NULL: the next population's coherence key box
     // power cutoff (the CUT instantiations only): see CompactArgs
     float cut;
-    uint32_t bud_tri;                 // BUD only, surface map on: the records hold a seventh array behind
+    uint32_t bud_tri;                 // BUD only: LPC_REC_TRI / LPC_REC_DEST, the arrays the records hold behind
                                       //   bud.kt at stride cst (these four bytes were padding)
     uint32_t *tcc;                    // [ntiles] culled children
     double *tcp;                      // [ntiles] their power

@@ -1546,8 +1546,9 @@ __global__ __launch_bounds__(256) void k_shade(ShadeArgs A)
 // The power budget's fate record of ray r (BudgetRec; lpc.h has the ledger's
 // rule): pin is the power the shading read, po / s what it made of the ray.  The
 // dissipation test is shade()'s own (.cl:385-394).
-static __device__ __forceinline__ void budget_record(const BudgetRec &B, int32_t *tri, const ShadeArgs &A, int64_t r,
-                                                     float pin, const PostOut &po, const ShadeOut &s)
+static __device__ __forceinline__ void budget_record(const BudgetRec &B, int32_t *tri, float *dst, int64_t stride,
+                                                     f3 dest, const ShadeArgs &A, int64_t r, float pin,
+                                                     const PostOut &po, const ShadeOut &s)
 {
     const bool dis = po.n1 >= 0 && A.mat_type[po.n1] == 0 && A.diss[po.n1] > 0.000001f;
     B.dn[r] = dis ? po.n1 : -1;
@@ -1557,19 +1558,23 @@ static __device__ __forceinline__ void budget_record(const BudgetRec &B, int32_t
     B.kr[r] = s.r_meas == 0 ? s.r_pow : 0.0f;
     B.kt[r] = s.t_meas == 0 ? s.t_pow : 0.0f;
     if (tri) tri[r] = po.hit_idx;       // the surface map's seventh array
+    if (dst) {                          // the volume map's dest, the value shade() measured ray_len from
+        dst[r] = dest.x; dst[stride + r] = dest.y; dst[2 * stride + r] = dest.z;
+    }
 }
 
 // k_shade with the power budget on: the same shading and stores, and the ray's
 // fate record.
 template <int KU>
-__global__ __launch_bounds__(256) void k_shade_bud(ShadeArgs A, BudgetRec B, int32_t *tri)
+__global__ __launch_bounds__(256) void k_shade_bud(ShadeArgs A, BudgetRec B, int32_t *tri, float *dst, int64_t stride)
 {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= A.n) return;
     const float pin = A.in.pw[r];
     PostOut po;
     const ShadeOut s = shade_ray<KU>(A, r, &po);
-    budget_record(B, tri, A, r, pin, po, s);
+    // (dest as shade_ray stored it: the float32 values shade() read)
+    budget_record(B, tri, dst, stride, mk3(A.o.destx[r], A.o.desty[r], A.o.destz[r]), A, r, pin, po, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -1824,7 +1829,8 @@ static __device__ __forceinline__ int tile_tid()
 // and per-tile arrays exist only in that instantiation.
 // BUD: the power budget's instantiation (lpc_trace_set_budget): every ray's fate
 // record (six stores, taken before the cutoff) for k_budget_sum; with the surface
-// map on (lpc_trace_set_surface) a seventh, the hit triangle, for k_surface_sum.
+// map on (lpc_trace_set_surface) a seventh, the hit triangle, for k_surface_sum;
+// with the volume map on (lpc_trace_set_volume) dest, for k_volume_sum.
 template <int KU, bool DS, bool CUT = false, bool BUD = false>
 __global__ __launch_bounds__(LPC_ST_TILE) void k_shade_stage(StageArgs A)
 {
@@ -1880,8 +1886,11 @@ __global__ __launch_bounds__(LPC_ST_TILE) void k_shade_stage(StageArgs A)
         }
     }
     if constexpr (BUD) {
-        // (the seventh array lies behind the sixth, at the records' stride)
-        if (in) budget_record(A.bud, A.bud_tri ? (int32_t *)(A.bud.kt + A.cst) : nullptr, S, r, S.in.pw[r], po, s);
+        // (the seventh array lies behind the sixth, at the records' stride; dest behind the seventh)
+        if (in)
+            budget_record(A.bud, (A.bud_tri & LPC_REC_TRI) ? (int32_t *)(A.bud.kt + A.cst) : nullptr,
+                          (A.bud_tri & LPC_REC_DEST) ? A.bud.kt + 2 * A.cst : nullptr, A.cst, dest, S, r, S.in.pw[r],
+                          po, s);
     }
     bool fR = in && s.r_meas == 0, fT = in && s.t_meas == 0;
     const bool fM = in && s.meas == 1;
@@ -2540,6 +2549,94 @@ __global__ __launch_bounds__(256) void k_surface_commit(double *inc_tot, double 
 {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
         if (cnt[i]) { inc_tot[i] += inc[i]; dep_tot[i] += dep[i]; cnt_tot[i] += cnt[i]; }
+}
+
+// The volume map of one chunk: every record with dn >= 0 walks its segment
+// through the voxel grid (lpc_math.hpp volume_begin / volume_step; lpc.h has the
+// rule) and books its shares into the iteration's staging table.
+//   * One record per lane, grid-stride.  The lanes of a wave step their own
+//     segments in lock step until the wave's ballot of unfinished lanes is
+//     empty: whole waves take every step, a finished lane idles.
+//   * Populations come in coherence order, so neighbouring lanes cross the same
+//     voxels: adds merge in a direct-mapped LDS table keyed by voxel %
+//     LPC_VOL_LDS.  A lane claims its entry by compare-and-swap on the tag (-1:
+//     free) and adds there; an entry owned by another voxel sends the add to
+//     the staging table directly.  The block flushes its claimed entries once,
+//     at its end, so a voxel crossed by a whole block costs one global atomic.
+//   * `outside` and the segment count are summed per lane, reduced per wave and
+//     added once per block (entries V and V + 1 of the table).
+// The float64 sums depend on the adds' order in their last bits; the count is
+// exact.  Device-sized launches read the record count on the device.
+__global__ __launch_bounds__(256) void k_volume_sum(VolumeSumArgs A)
+{
+    __shared__ double s_dep[LPC_VOL_LDS];
+    __shared__ int32_t s_tag[LPC_VOL_LDS];
+    __shared__ double s_out[4];
+    __shared__ unsigned int s_seg[4];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    int64_t n = A.n;
+    if (A.nd) {
+        const long long nd = *A.nd;
+        n = nd > 0 ? min((int64_t)nd, A.n) : 0;
+    }
+    for (int i = t; i < LPC_VOL_LDS; i += 256) { s_dep[i] = 0.0; s_tag[i] = -1; }
+    __syncthreads();
+    const lpc::VolumeGrid G = A.G;
+    double outside = 0.0;
+    unsigned int seg = 0u;
+    auto book = [&](int32_t v, double share) {
+        if (v < 0 || (int64_t)v >= A.V) { outside += share; return; }   // (v >= V: never expected)
+        const int e = v & (LPC_VOL_LDS - 1);
+        const int32_t old = atomicCAS(&s_tag[e], -1, v);
+        if (old == -1 || old == v) atomicAdd(&s_dep[e], share);
+        else atomicAdd(&A.dep[v], share);
+    };
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < n; base += (int64_t)gridDim.x * 256) {
+        const int64_t r = base + t;
+        lpc::VolumeWalk w;
+        w.done = true;
+        if (r < n) {
+            const int32_t dn = A.dn[r];
+            if (dn >= 0) {
+                const double O[3] = {(double)A.ox[r], (double)A.oy[r], (double)A.oz[r]};
+                const double E[3] = {(double)A.ex[r], (double)A.ey[r], (double)A.ez[r]};
+                const double D = (double)A.pin[r] - (double)A.p[r];
+                const double ex = E[0] - O[0], ey = E[1] - O[1], ez = E[2] - O[2];
+                // (dn < K: budget_record took it from the scene's own media)
+                const double a = (double)A.diss[dn < A.K ? dn : 0] * sqrt((ex * ex + ey * ey) + ez * ez);
+                ++seg;
+                lpc::volume_begin(w, G, O, E, a, D, book);
+            }
+        }
+        while (__ballot(!w.done)) (void)lpc::volume_step(w, G, book);
+    }
+    // `outside` and the count: per wave, then once per block
+    outside = wave_sum(outside);
+    for (int o = 32; o >= 1; o >>= 1) seg += __shfl_xor(seg, o, 64);
+    if (lane == 0) { s_out[wv] = outside; s_seg[wv] = seg; }
+    __syncthreads();
+    if (t == 0) {
+        const unsigned int sg = s_seg[0] + s_seg[1] + s_seg[2] + s_seg[3];
+        if (sg) {
+            atomicAdd(&A.dep[A.V], ((s_out[0] + s_out[1]) + s_out[2]) + s_out[3]);
+            atomicAdd(&A.dep[A.V + 1], (double)sg);
+        }
+    }
+    for (int i = t; i < LPC_VOL_LDS; i += 256) {
+        const int32_t v = s_tag[i];
+        if (v >= 0) atomicAdd(&A.dep[v], s_dep[i]);
+    }
+}
+
+// A collected iteration's staging table into the trace's (the rule of
+// k_budget_commit: only iterations the trace keeps are added).  An entry the
+// iteration left at +0.0 is skipped: most of a grid, on most iterations.
+__global__ __launch_bounds__(256) void k_volume_commit(double *tot, const double *st, int64_t n)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double v = st[i];
+        if (__double_as_longlong(v) != 0ll) tot[i] += v;
+    }
 }
 
 // Population copy (trace reset: emitted rays -> current population), one launch.

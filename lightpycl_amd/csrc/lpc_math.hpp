@@ -382,6 +382,135 @@ LPC_HD int bin_index(double v, const double *e, int nb)
 }
 
 // ---------------------------------------------------------------------------
+// The volume map's walk of one dissipating segment through the voxel grid
+// (include/lpc.h has the rule).  Everything is float64.
+// A walk is a small state machine so that a wave's lanes can step their own
+// segments in lock step: volume_begin() books what needs no stepping (the
+// degenerate cases, the part of [0,1] in front of the box) and volume_step()
+// books one interval and moves one voxel on; it returns true when the walk has
+// ended, having booked the part behind the box.  book(voxel, share) is called
+// with voxel -1 for `outside`.  The shares telescope: they sum to D (W(1) -
+// W(0)) = D whatever the rounding of the crossing parameters.
+struct VolumeGrid {
+    double lo[3], hi[3];
+    int32_t n[3];
+    int32_t pad;
+};
+struct VolumeWalk {
+    double ox, oy, oz, dx, dy, dz;      // X(s) = O + s d
+    double tx, ty, tz;                  // the next crossing parameter per axis (+inf: the axis never steps)
+    double a, em, D;                    // em = expm1(-a)
+    double s, W, s1;                    // the walk's position, W(s), the end of the clipped part
+    int32_t ix, iy, iz, sx, sy, sz;     // the voxel, the step per axis (0: zero extent)
+    int32_t left;                       // steps the walk may still take (a bound, never reached)
+    bool done;
+};
+LPC_HD double volume_W(const VolumeWalk &w, double s)
+{
+    if (s <= 0.0) return 0.0;
+    if (s >= 1.0) return 1.0;
+    return w.a > 0.0 ? expm1(-w.a * s) / w.em : s;
+}
+// The k-th edge of an axis, the rule's own expression.
+LPC_HD double volume_edge(double lo, double hi, int32_t n, int32_t k) { return lo + ((double)k * (hi - lo)) / (double)n; }
+LPC_HD int32_t volume_cell(double p, double lo, double hi, int32_t n)
+{
+    int32_t i = (int32_t)floor((p - lo) * ((double)n / (hi - lo)));
+    if (i > n - 1) i = n - 1;
+    if (i < 0) i = 0;
+    // (the product above may round across an edge: the edges decide)
+    if (i > 0 && p < volume_edge(lo, hi, n, i)) --i;
+    else if (i < n - 1 && p >= volume_edge(lo, hi, n, i + 1)) ++i;
+    return i;
+}
+LPC_HD double volume_next(double o, double d, double lo, double hi, int32_t n, int32_t i, int32_t step)
+{
+    if (step == 0) return INFINITY;
+    return (volume_edge(lo, hi, n, step > 0 ? i + 1 : i) - o) / d;
+}
+template <class Fn>
+LPC_HD void volume_begin(VolumeWalk &w, const VolumeGrid &G, const double *O, const double *E, double a, double D,
+                         Fn book)
+{
+    w.done = true;
+    w.a = a; w.D = D; w.em = 0.0; w.s = 0.0; w.W = 0.0; w.s1 = 1.0; w.left = 0;
+    w.ix = w.iy = w.iz = 0; w.sx = w.sy = w.sz = 0;
+    w.tx = w.ty = w.tz = INFINITY;
+    w.ox = O[0]; w.oy = O[1]; w.oz = O[2];
+    w.dx = E[0] - O[0]; w.dy = E[1] - O[1]; w.dz = E[2] - O[2];
+    const bool fin = isfinite(w.ox) && isfinite(w.oy) && isfinite(w.oz) && isfinite(w.dx) && isfinite(w.dy) &&
+                     isfinite(w.dz) && isfinite(E[0]) && isfinite(E[1]) && isfinite(E[2]) && isfinite(a);
+    if (!fin) { book(-1, D); return; }
+    // the part of [0,1] inside the box: the three slabs (a zero extent: inside its slab or nowhere)
+    double s0 = 0.0, s1 = 1.0;
+    bool in = true;
+    auto slab = [&](double o, double d, double lo, double hi) {
+        if (d == 0.0) { if (o < lo || o > hi) in = false; return; }
+        double t0 = (lo - o) / d, t1 = (hi - o) / d;
+        if (t0 > t1) { const double t = t0; t0 = t1; t1 = t; }
+        if (t0 > s0) s0 = t0;
+        if (t1 < s1) s1 = t1;
+    };
+    slab(w.ox, w.dx, G.lo[0], G.hi[0]);
+    slab(w.oy, w.dy, G.lo[1], G.hi[1]);
+    slab(w.oz, w.dz, G.lo[2], G.hi[2]);
+    const bool point = w.dx == 0.0 && w.dy == 0.0 && w.dz == 0.0;
+    if (!in || (!point && !(s0 < s1))) { book(-1, D); return; }
+    w.ix = volume_cell(w.ox + s0 * w.dx, G.lo[0], G.hi[0], G.n[0]);
+    w.iy = volume_cell(w.oy + s0 * w.dy, G.lo[1], G.hi[1], G.n[1]);
+    w.iz = volume_cell(w.oz + s0 * w.dz, G.lo[2], G.hi[2], G.n[2]);
+    if (point) { book((w.ix * G.n[1] + w.iy) * G.n[2] + w.iz, D); return; }   // E == O: the whole D
+    if (a > 0.0) w.em = expm1(-a);
+    w.sx = w.dx > 0.0 ? 1 : (w.dx < 0.0 ? -1 : 0);
+    w.sy = w.dy > 0.0 ? 1 : (w.dy < 0.0 ? -1 : 0);
+    w.sz = w.dz > 0.0 ? 1 : (w.dz < 0.0 ? -1 : 0);
+    w.tx = volume_next(w.ox, w.dx, G.lo[0], G.hi[0], G.n[0], w.ix, w.sx);
+    w.ty = volume_next(w.oy, w.dy, G.lo[1], G.hi[1], G.n[1], w.iy, w.sy);
+    w.tz = volume_next(w.oz, w.dz, G.lo[2], G.hi[2], G.n[2], w.iz, w.sz);
+    w.s = s0; w.s1 = s1;
+    w.W = volume_W(w, s0);
+    if (s0 > 0.0) book(-1, D * w.W);                                        // in front of the box
+    w.left = G.n[0] + G.n[1] + G.n[2] + 8;
+    w.done = false;
+}
+template <class Fn>
+LPC_HD bool volume_step(VolumeWalk &w, const VolumeGrid &G, Fn book)
+{
+    if (w.done) return true;
+    // the nearest crossing ends the interval in this voxel
+    const int ax = (w.tx <= w.ty && w.tx <= w.tz) ? 0 : (w.ty <= w.tz ? 1 : 2);
+    const double tn = ax == 0 ? w.tx : (ax == 1 ? w.ty : w.tz);
+    const bool last = !(tn < w.s1);
+    const double sn = last ? w.s1 : tn;
+    if (sn > w.s) {
+        const double Wn = volume_W(w, sn);
+        book((w.ix * G.n[1] + w.iy) * G.n[2] + w.iz, w.D * (Wn - w.W));
+        w.s = sn; w.W = Wn;
+    }
+    bool end = last || --w.left <= 0;
+    if (!end) {
+        if (ax == 0) {
+            w.ix += w.sx;
+            end = (uint32_t)w.ix >= (uint32_t)G.n[0];
+            if (!end) w.tx = volume_next(w.ox, w.dx, G.lo[0], G.hi[0], G.n[0], w.ix, w.sx);
+        } else if (ax == 1) {
+            w.iy += w.sy;
+            end = (uint32_t)w.iy >= (uint32_t)G.n[1];
+            if (!end) w.ty = volume_next(w.oy, w.dy, G.lo[1], G.hi[1], G.n[1], w.iy, w.sy);
+        } else {
+            w.iz += w.sz;
+            end = (uint32_t)w.iz >= (uint32_t)G.n[2];
+            if (!end) w.tz = volume_next(w.oz, w.dz, G.lo[2], G.hi[2], G.n[2], w.iz, w.sz);
+        }
+    }
+    if (end) {
+        if (w.s < 1.0) book(-1, w.D * (1.0 - w.W));                          // behind the box
+        w.done = true;
+    }
+    return end;
+}
+
+// ---------------------------------------------------------------------------
 // Elevation of a measured position against a pole, as the beam analyses
 // (iterative_tracer.py:420-501) evaluate it with numpy on float32 (n,4) rows and a
 // float64 pole: arccos(dot(pos / norm(pos, axis=1), pole)).

@@ -256,8 +256,8 @@ struct StagedTable : LedgerBuf {
 };
 // Which ledgers an iteration runs with (the switches as they stood at its enqueue).
 struct LedgerSet {
-    bool cut = false, bud = false, surf = false;
-    bool rec() const { return bud || surf; }        // the shading's BUD instantiations write the fate records
+    bool cut = false, bud = false, surf = false, vol = false;
+    bool rec() const { return bud || surf || vol; } // the shading's BUD instantiations write the fate records
 };
 struct Ledgers {
     float min_power = 0.0f;                         // lpc_trace_set_min_power; 0: off (the compaction's default
@@ -271,8 +271,13 @@ struct Ledgers {
     LedgerBuf bud;                                  // lpc_trace_budget: BudgetRow rows ...
     StagedTable bud_mesh{2};                        // ... and per mesh: power, count of [K][4]
     StagedTable surf{3};                            // lpc_trace_surface: incident, deposited, count of [M]
+    bool volume = false;                            // lpc_trace_set_volume; off: no dest in the fate records
+    lpc::VolumeGrid vgrid = {};                     // the grid last set (dims 0: never), kept when the map goes off
+    int64_t vV = 0;                                 // its voxels
+    StagedTable vol{1};                             // lpc_trace_volume: [V + 2], the voxels, outside, segments
     DBuf w_rec;                                     // fate records of one chunk (BudgetRec: 6 arrays of ws_rays, 7
-                                                    //   with the surface map on): the budget or the map on
+                                                    //   with the surface map on, 10 with the volume map on): a
+                                                    //   ledger that reads them on
 };
 
 // Every GPU resource of the handle is held by an owner of lpc_resource.hpp and
@@ -525,7 +530,7 @@ static int ledgers_clear(lpc_handle *h)
     Ledgers &G = h->led;
     G.it_done = 0;
     G.bud_seen = false;
-    for (LedgerBuf *b : std::initializer_list<LedgerBuf *>{&G.cull, &G.bud, &G.bud_mesh, &G.surf}) {
+    for (LedgerBuf *b : std::initializer_list<LedgerBuf *>{&G.cull, &G.bud, &G.bud_mesh, &G.surf, &G.vol}) {
         if (b->dirty && b->buf.p) HIPCHK(h, hipMemsetAsync(b->buf.p, 0, b->buf.bytes, h->stream));
         b->dirty = false;
     }
@@ -2423,6 +2428,86 @@ int lpc_trace_surface(lpc_handle *h, double *incident, double *deposited, int64_
     return staged_read(h, h->led.surf, M, {incident, deposited, count});
 }
 
+static_assert(LPC_VOL_LDS == LPC_VOLUME_LDS_ENTRIES, "lpc.h states k_volume_sum's LDS table size");
+static_assert((LPC_VOL_LDS & (LPC_VOL_LDS - 1)) == 0, "k_volume_sum maps a voxel by its low bits");
+
+// A grid as lpc.h admits it -> its voxel count, or 0.
+static int64_t volume_grid(const double *lo3, const double *hi3, const int32_t *dims3, lpc::VolumeGrid *G)
+{
+    int64_t V = 1;
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(lo3[k]) || !std::isfinite(hi3[k]) || !(lo3[k] < hi3[k]) || !std::isfinite(hi3[k] - lo3[k]))
+            return 0;
+        if (dims3[k] < 1 || dims3[k] > 1024) return 0;
+        G->lo[k] = lo3[k]; G->hi[k] = hi3[k]; G->n[k] = dims3[k];
+        V *= dims3[k];
+    }
+    G->pad = 0;
+    return V <= ((int64_t)1 << 27) ? V : 0;
+}
+
+int lpc_trace_set_volume(lpc_handle *h, const double *lo3, const double *hi3, const int32_t *dims3)
+{
+    if (!h) return set_err(nullptr, LPC_E_ARG, "null handle");
+    Ledgers &G = h->led;
+    if (!lo3) { G.volume = false; return 0; }       // from the next launched iteration; the grid stays readable
+    if (!hi3 || !dims3) return set_err(h, LPC_E_ARG, "trace_set_volume: null argument");
+    lpc::VolumeGrid g = {};
+    const int64_t V = volume_grid(lo3, hi3, dims3, &g);
+    if (!V)
+        return set_err(h, LPC_E_ARG, "trace_set_volume: a grid needs finite lo < hi, dims in 1..1024 and at most 2^27 voxels");
+    if (memcmp(&g, &G.vgrid, sizeof(g)) != 0 && G.vol.dirty) {      // what was booked belongs to another grid
+        HIPCHK(h, hipSetDevice(h->device));
+        if (G.vol.buf.p) HIPCHK(h, hipMemsetAsync(G.vol.buf.p, 0, G.vol.buf.bytes, h->stream));
+        G.vol.dirty = false;
+    }
+    G.vgrid = g; G.vV = V;
+    G.volume = true;
+    return 0;
+}
+
+int lpc_trace_volume(lpc_handle *h, double *deposited, int64_t cap, int32_t *dims3, double *outside, int64_t *segments)
+{
+    if (!h || !dims3) return set_err(h, LPC_E_ARG, "null argument");
+    const Ledgers &G = h->led;
+    for (int k = 0; k < 3; ++k) dims3[k] = G.vgrid.n[k];
+    const int64_t V = G.vV;
+    if (deposited && cap < V) return set_err(h, LPC_E_ARG, "trace_volume: capacity below the grid's voxel count");
+    RETIF(settle(h));
+    if (deposited && V > 0) memset(deposited, 0, (size_t)V * 8);
+    double tail[2] = {0.0, 0.0};
+    const StagedTable &T = G.vol;
+    if (T.dirty && T.live() && T.n == V + 2) {
+        HIPCHK(h, hipSetDevice(h->device));
+        if (deposited)
+            HIPCHK(h, hipMemcpyAsync(deposited, T.total(), (size_t)V * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(tail, T.total() + V, 16, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    if (outside) *outside = tail[0];
+    if (segments) *segments = (int64_t)llrint(tail[1]);
+    return 0;
+}
+
+int lpc_volume_segment_host(const double *lo3, const double *hi3, const int32_t *dims3, const double *O3,
+                            const double *E3, double a, double D, int64_t *idx, double *share, int64_t cap, int64_t *n)
+{
+    if (!lo3 || !hi3 || !dims3 || !O3 || !E3 || !n || cap < 0 || (cap > 0 && (!idx || !share)))
+        return set_err(nullptr, LPC_E_ARG, "volume_segment_host: bad argument");
+    lpc::VolumeGrid g = {};
+    if (!volume_grid(lo3, hi3, dims3, &g)) return set_err(nullptr, LPC_E_ARG, "volume_segment_host: bad grid");
+    int64_t m = 0;
+    auto book = [&](int32_t v, double s) {
+        if (m < cap) { idx[m] = v; share[m] = s; }
+        ++m;
+    };
+    lpc::VolumeWalk w;
+    lpc::volume_begin(w, g, O3, E3, a, D, book);
+    while (!lpc::volume_step(w, g, book)) {}
+    *n = m;                             // (beyond cap: the count needed, the first cap intervals written)
+    return 0;
+}
+
 int lpc_shm_comm_open(const char *name, int32_t rank, int32_t world, int32_t create, lpc_shm_comm **out)
 {
     if (!out) return set_err(nullptr, LPC_E_ARG, "shm comm: null output");
@@ -2634,9 +2719,12 @@ struct LedgerPlan {
     LedgerSet on;
     BudgetRec R = {};
     int32_t *tri = nullptr;
+    float *dest = nullptr;                  // arrays eight to ten (volume map on, else NULL)
     CullSumArgs CS = {};
     BudgetSumArgs BS = {};
     SurfaceSumArgs SS = {};
+    VolumeSumArgs VS = {};
+    uint32_t rec_mask() const { return (tri ? LPC_REC_TRI : 0u) | (dest ? LPC_REC_DEST : 0u); }
 };
 
 // What the chunks of one enqueued iteration share.
@@ -2655,16 +2743,18 @@ struct IterPlan {
     LedgerPlan L;                           // the ledgers it runs with (ledgers_setup)
 };
 
-// The fate records of one chunk, for the power budget or the surface map: six
-// arrays of ws_rays, and the hit triangle with the map on.
+// The fate records of one chunk, for the ledgers that read them: six arrays of
+// ws_rays, the hit triangle with the surface map on, dest with the volume map
+// on (at fixed positions: the hit triangle's array is then there, written or not).
 static int fate_records(lpc_handle *h, LedgerPlan *L)
 {
     const size_t C = (size_t)h->ws_rays;
-    RETIF(dalloc(h, h->led.w_rec, (L->on.surf ? 7 : 6) * C * 4));
+    RETIF(dalloc(h, h->led.w_rec, (L->on.vol ? 10 : L->on.surf ? 7 : 6) * C * 4));
     float *f = (float *)h->led.w_rec.p;
     L->R.dn = (int32_t *)f; L->R.hit = (int32_t *)(f + C);
     L->R.pin = f + 2 * C; L->R.p = f + 3 * C; L->R.kr = f + 4 * C; L->R.kt = f + 5 * C;
     if (L->on.surf) L->tri = (int32_t *)(f + 6 * C);
+    if (L->on.vol) L->dest = f + 7 * C;
     return 0;
 }
 
@@ -2679,7 +2769,7 @@ static int ledgers_setup(lpc_handle *h, IterPlan *I, Pending *P)
 {
     Ledgers &G = h->led;
     LedgerPlan &L = I->L = LedgerPlan();
-    const LedgerSet on = P->on = L.on = LedgerSet{G.min_power > 0.0f, G.budget, G.surface};
+    const LedgerSet on = P->on = L.on = LedgerSet{G.min_power > 0.0f, G.budget, G.surface, G.volume};
     const int64_t slot = P->slot;
     const int par = (int)(slot & 1);
     if ((on.cut || on.bud) && slot >= kCullSlots)
@@ -2719,15 +2809,32 @@ static int ledgers_setup(lpc_handle *h, IterPlan *I, Pending *P)
         RETIF(staged_zero(h, T, par));
         T.dirty = true;
     }
+    if (on.vol) {                       // the per-voxel staging table [V + 2]: the voxels, outside, segments
+        StagedTable &T = G.vol;
+        RETIF(staged_shape(h, T, G.vV + 2));
+        const size_t C = (size_t)h->ws_rays;
+        L.VS.dn = L.R.dn; L.VS.pin = L.R.pin; L.VS.p = L.R.p;
+        L.VS.ex = L.dest; L.VS.ey = L.dest + C; L.VS.ez = L.dest + 2 * C;
+        L.VS.diss = (const float *)h->scene.d_diss.p;
+        L.VS.K = h->scene.K;
+        L.VS.G = G.vgrid; L.VS.V = G.vV;
+        L.VS.dep = T.staging(par);
+        RETIF(staged_zero(h, T, par));
+        T.dirty = true;
+    }
     return 0;
 }
 
 // A chunk's sums into the iteration's ledgers: the culled sums of the
 // compaction's tiles (`tile` rays each; off the counters' publication) and the
 // sums over the fate records.  A fused chunk takes both at its end; a plain
-// chunk has its records after the shading and its tiles after k_count.
+// chunk has its records after the shading and its tiles after k_count.  in: the
+// chunk's rays as the shading read them (the volume map's origins; on this
+// stream nothing writes those rows before the next chunk's or iteration's
+// intersect stage).
 enum : unsigned { kSumCulled = 1, kSumRecords = 2 };
-static void ledgers_sum(lpc_handle *h, const IterPlan &I, int64_t base, int64_t nc, int tile, unsigned what)
+static void ledgers_sum(lpc_handle *h, const IterPlan &I, const RaysIn &in, int64_t base, int64_t nc, int tile,
+                        unsigned what)
 {
     const LedgerPlan &L = I.L;
     if ((what & kSumCulled) && L.on.cut) {
@@ -2748,6 +2855,12 @@ static void ledgers_sum(lpc_handle *h, const IterPlan &I, int64_t base, int64_t 
         SS.n = nc; SS.nd = I.nd();
         hipLaunchKernelGGL(k_surface_sum, dim3(nb), dim3(256), 0, h->stream, SS);
     }
+    if (L.on.vol) {
+        VolumeSumArgs VS = L.VS;
+        VS.ox = in.ox; VS.oy = in.oy; VS.oz = in.oz;
+        VS.n = nc; VS.nd = I.nd();
+        hipLaunchKernelGGL(k_volume_sum, dim3(nb), dim3(256), 0, h->stream, VS);
+    }
 }
 
 // A collected iteration's staging tables into the trace's (the kernels differ:
@@ -2755,7 +2868,7 @@ static void ledgers_sum(lpc_handle *h, const IterPlan &I, int64_t base, int64_t 
 static int ledgers_commit(lpc_handle *h, const Pending &P)
 {
     const int par = (int)(P.slot & 1);
-    const StagedTable &B = h->led.bud_mesh, &S = h->led.surf;
+    const StagedTable &B = h->led.bud_mesh, &S = h->led.surf, &W = h->led.vol;
     if (P.on.bud && B.live()) {
         double *tot = B.total(), *st = B.staging(par);
         hipLaunchKernelGGL(k_budget_commit, dim3((unsigned)std::min<int64_t>((B.n + 255) / 256, 64)), dim3(256), 0,
@@ -2769,6 +2882,12 @@ static int ledgers_commit(lpc_handle *h, const Pending &P)
         hipLaunchKernelGGL(k_surface_commit, dim3((unsigned)std::min<int64_t>((S.n + 255) / 256, 1024)), dim3(256), 0,
                            h->stream, tot, S.col(tot, 1), (unsigned long long *)S.col(tot, 2), (const double *)st,
                            (const double *)S.col(st, 1), (const unsigned long long *)S.col(st, 2), (int)S.n);
+        HIPCHK(h, hipGetLastError());
+        h->inflight = true;
+    }
+    if (P.on.vol && W.live()) {
+        hipLaunchKernelGGL(k_volume_commit, dim3((unsigned)std::min<int64_t>((W.n + 255) / 256, 4096)), dim3(256), 0,
+                           h->stream, W.total(), (const double *)W.staging(par), W.n);
         HIPCHK(h, hipGetLastError());
         h->inflight = true;
     }
@@ -2809,7 +2928,7 @@ static int enqueue_fused_chunk(lpc_handle *h, const IterPlan &I, const RaysIn &i
     G.tmask = tmask;
     G.tbox = I.want_box ? (uint32_t *)h->w_tbox.p : nullptr;
     G.cut = h->led.min_power; G.tcc = (uint32_t *)I.L.CS.cc; G.tcp = (double *)I.L.CS.cp;
-    G.bud = I.L.R; G.bud_tri = I.L.tri ? 1u : 0u;       // (the records' stride is cst: both are ws_rays)
+    G.bud = I.L.R; G.bud_tri = I.L.rec_mask();          // (the records' stride is cst: both are ws_rays)
     // (this nesting keeps the instantiations in their order in the code object;
     // the power budget's come after the others)
     auto launch_stage = [&](auto bud) {
@@ -2853,7 +2972,7 @@ static int enqueue_fused_chunk(lpc_handle *h, const IterPlan &I, const RaysIn &i
     with_bool(ds != nullptr, [&](auto dsz) {
         hipLaunchKernelGGL(k_stage_move<decltype(dsz)::value>, dim3((unsigned)nt), dim3(LPC_ST_TILE), 0, h->stream, M);
     });
-    ledgers_sum(h, I, base, nc, LPC_ST_TILE, kSumCulled | kSumRecords);
+    ledgers_sum(h, I, in, base, nc, LPC_ST_TILE, kSumCulled | kSumRecords);
     // k_shade_stage restored what it read, k_stage_move reset the next launch's words
     h->slots = SlotState{/*clean*/ true, h->emitted.max_ray_len, /*misc_clean*/ true};
     HIPCHK(h, hipGetLastError());
@@ -2904,17 +3023,17 @@ static int enqueue_plain_chunk(lpc_handle *h, const IterPlan &I, const IterOut &
         const ShadeArgs SA = shade_args(h, in, nullptr, nc, h->emitted.max_ray_len, h->emitted.ior_env, false);
         with_ku(h->scene.K, [&](auto ku) {
             hipLaunchKernelGGL(k_shade_bud<decltype(ku)::value>, dim3(grid1(nc)), dim3(256), 0, h->stream, SA, I.L.R,
-                               I.L.tri);
+                               I.L.tri, I.L.dest, (int64_t)h->ws_rays);
         });
         HIPCHK(h, hipGetLastError());
-        ledgers_sum(h, I, base, nc, 1024, kSumRecords);
+        ledgers_sum(h, I, in, base, nc, 1024, kSumRecords);
     } else {
         RETIF(run_shade(h, in, nullptr, nc, h->emitted.max_ray_len, h->emitted.ior_env, false));
     }
     with_bool(I.L.on.cut, [&](auto ct) {
         hipLaunchKernelGGL(k_count<decltype(ct)::value>, dim3((unsigned)A.nb), dim3(256), 0, h->stream, A);
     });
-    ledgers_sum(h, I, base, nc, 1024, kSumCulled);
+    ledgers_sum(h, I, in, base, nc, 1024, kSumCulled);
     if (O.X) {
         const double hx = h->knobs.host_prof ? host_us() : 0.0;
         RETIF(export_chunk(h, in, o, nc, base, I.N, *O.X));

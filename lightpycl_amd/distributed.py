@@ -151,7 +151,7 @@ class ShmComm:
             pass
 
 
-SURFACE_PIECE = 1 << 20     # float64 values per exchange of the surface map's tables (ShardedTrace.run)
+SURFACE_PIECE = 1 << 20     # float64 values per exchange of the surface and volume maps' tables (ShardedTrace.run)
 
 
 def shard_bounds(n, rank, world):

@@ -199,6 +199,7 @@ class Engine:
         self.min_power = 0.0
         self.budget_on = False
         self.surface_on = False
+        self.volume_on = False
 
     # -- lifecycle -----------------------------------------------------------
     def close(self):
@@ -437,6 +438,42 @@ class Engine:
         cnt = np.zeros(m.value, np.int64)
         self._c(self.L.lpc_trace_surface(self.h, ptr(inc), ptr(dep), ptr(cnt), m.value, ctypes.byref(m)))
         return {"incident": inc, "deposited": dep, "count": cnt}
+
+    def set_volume(self, lo, hi=None, shape=None):
+        """lpc_trace_set_volume: keep the volume map (off by default) on the grid
+        of ``shape`` = (nx, ny, nz) voxels over the box ``lo`` .. ``hi`` (float64
+        triples); ``set_volume(None)`` switches it off.  Holds until changed, from
+        the next launched iteration; another grid discards what the current trace
+        booked."""
+        if lo is None:
+            self._c(self.L.lpc_trace_set_volume(self.h, None, None, None))
+            self.volume_on = False
+            return
+        lo3 = np.ascontiguousarray(np.asarray(lo, np.float64).reshape(3))
+        hi3 = np.ascontiguousarray(np.asarray(hi, np.float64).reshape(3))
+        shp = np.asarray(shape).reshape(3)
+        if not np.all((shp >= 1) & (shp <= _lib.VOLUME_MAX_DIM)):
+            raise _lib.LpcError(f"set_volume: shape {tuple(int(v) for v in shp)} outside 1..{_lib.VOLUME_MAX_DIM}")
+        dims = np.ascontiguousarray(shp, np.int32)
+        self._c(self.L.lpc_trace_set_volume(self.h, ptr(lo3), ptr(hi3), ptr(dims)))
+        self.volume_on = True
+        self.volume_grid = (lo3, hi3, tuple(int(v) for v in dims))
+
+    def volume(self):
+        """lpc_trace_volume: the volume map of the current trace on the grid last
+        set -> a dict of ``deposited`` (float64, shape (nx, ny, nz)), ``outside``
+        (float), ``segments`` (int), ``lo``, ``hi`` (float64 triples) and
+        ``shape``.  Zeros when the trace ran with the map off; an empty map when
+        no grid was ever set."""
+        dims = np.zeros(3, np.int32)
+        self._c(self.L.lpc_trace_volume(self.h, None, 0, ptr(dims), None, None))
+        shape = tuple(int(v) for v in dims)
+        dep = np.zeros(int(np.prod(dims, dtype=np.int64)), np.float64)
+        out, seg = ctypes.c_double(0.0), ctypes.c_int64(0)
+        self._c(self.L.lpc_trace_volume(self.h, ptr(dep), dep.size, ptr(dims), ctypes.byref(out), ctypes.byref(seg)))
+        lo, hi = getattr(self, "volume_grid", (np.zeros(3), np.zeros(3), None))[:2]
+        return {"deposited": dep.reshape(shape), "outside": float(out.value), "segments": int(seg.value),
+                "lo": lo.copy(), "hi": hi.copy(), "shape": shape}
 
     def reset(self):
         self._c(self.L.lpc_trace_reset(self.h))

@@ -39,7 +39,7 @@ import numpy as np
 
 from . import _lib
 from .engine import Engine, _same_digest, array_digest, flatten_meshes, select_device
-from .ledgers import budget_dict, read_ledgers, surface_dict, triangle_areas  # noqa: F401 (re-exported)
+from .ledgers import budget_dict, read_ledgers, surface_dict, triangle_areas, volume_dict  # noqa: F401 (re-exported)
 
 
 def f32_sorted_sum(a):
@@ -147,7 +147,7 @@ class CL_Tracer:
 
     def iterative_tracer(self, light_source, meshes, trace_iterations=100, trace_until_dissipated=0.99,
                          max_ray_len=np.float32(1e3), ior_env=np.float32(1.0), keep_results=True,
-                         min_ray_power=0.0, power_budget=False, surface_map=False):
+                         min_ray_power=0.0, power_budget=False, surface_map=False, volume_map=None):
         """Trace until ``trace_iterations`` bounces, until less than
         (1 - trace_until_dissipated) of the input power is left, or until no ray is
         left (iterative_tracer.py:241-391).  Returns ``self.results``.
@@ -174,12 +174,23 @@ class CL_Tracer:
         ``surface_map=True`` (default off; set on every call) keeps the trace's
         surface map on the device: the power incident on and deposited in every
         triangle of the scene.  :meth:`surface_power` returns it afterwards
-        (DESIGN.md section 16).  The trace's results keep their bits likewise."""
+        (DESIGN.md section 16).  The trace's results keep their bits likewise.
+
+        ``volume_map=dict(lo=, hi=, shape=)`` (default None: off; set on every
+        call) keeps the trace's volume map on the device: the power dissipated
+        inside absorbing media per voxel of the grid of ``shape`` = (nx, ny, nz)
+        over the box ``lo`` .. ``hi``.  :meth:`volume_power` returns it afterwards
+        (DESIGN.md section 18).  The trace's results keep their bits likewise."""
         max_ray_len = np.float32(max_ray_len)
         ior_env = np.float32(ior_env)
         self.engine.set_min_power(min_ray_power)
         self.engine.set_budget(power_budget)
         self.engine.set_surface(surface_map)
+        if volume_map is None:
+            self.engine.set_volume(None)
+        else:
+            self.engine.set_volume(volume_map["lo"], volume_map["hi"], volume_map["shape"])
+        self._volume = None
         self._budget = None
         self._surface = None
         self.culled_counts, self.culled_power = [], []
@@ -293,6 +304,12 @@ class CL_Tracer:
         self.culled_power = led["culled_power"][:n] if "culled_power" in led else [0.0] * n
         self._budget = led.get("power_budget")
         self._surface = surface_dict(led["surface"], self.meshes) if "surface" in led else None
+        self._volume = volume_dict(led["volume"]) if "volume" in led else None
+
+    def volume_power(self):
+        """The volume map of the last trace (``volume_map=dict(...)``), see
+        :func:`volume_dict`; None when the trace ran without it."""
+        return getattr(self, "_volume", None)
 
     def surface_power(self):
         """The surface map of the last trace (``surface_map=True``), see

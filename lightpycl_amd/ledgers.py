@@ -1,6 +1,7 @@
 """The ledgers a trace keeps on the device (``Engine.set_min_power``,
-``set_budget``, ``set_surface``) as the Python layers return them:
-:func:`read_ledgers` at a trace's end, :func:`budget_dict`, :func:`surface_dict`."""
+``set_budget``, ``set_surface``, ``set_volume``) as the Python layers return
+them: :func:`read_ledgers` at a trace's end, :func:`budget_dict`,
+:func:`surface_dict`, :func:`volume_dict`."""
 from __future__ import annotations
 
 import math
@@ -64,6 +65,27 @@ def surface_dict(s, meshes):
     return out
 
 
+def volume_dict(v):
+    """The volume map as the tracer returns it, from ``Engine.volume()`` (or the
+    ranks' sum of it): where the power budget's ``dissipated`` landed.
+
+    ``deposited``: float64 (nx, ny, nz), the power dissipated in every voxel;
+    ``density`` = deposited / voxel volume; ``edges``: three float64 arrays of nx
+    + 1, ny + 1, nz + 1 voxel edges, ``lo + k (hi - lo) / n``; ``outside``: the
+    dissipated power that fell outside the grid's box; ``segments``: the rays
+    booked (int, the budget's summed ``n_dissipated``); ``total`` = sum(deposited)
+    + outside, the budget's ``dissipated`` summed over meshes and iterations."""
+    dep = np.asarray(v["deposited"], np.float64)
+    lo, hi = np.asarray(v["lo"], np.float64), np.asarray(v["hi"], np.float64)
+    edges = [lo[k] + np.arange(n + 1, dtype=np.float64) * (hi[k] - lo[k]) / n for k, n in enumerate(dep.shape)]
+    cell = float(np.prod((hi - lo) / np.asarray(dep.shape, np.float64))) if dep.size else 0.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        density = dep / cell
+    outside = float(v["outside"])
+    return {"deposited": dep, "density": density, "edges": edges, "outside": outside,
+            "segments": int(v["segments"]), "total": math.fsum(dep.ravel().tolist() + [outside])}
+
+
 def budget_dict(b, culled_counts=(), culled_power=()):
     """The power budget as the tracer returns it, from ``Engine.budget()`` and the
     culled-power ledger of the same trace (empty: no cutoff).
@@ -110,12 +132,14 @@ def read_ledgers(engine, reduce=None, iterations=None, piece=1 << 20):
     """The ledgers of the trace ``engine`` has just run -> a dict of those that
     are on (a reader waits for the stream): ``culled_counts`` / ``culled_power``
     per iteration with a cutoff set, ``power_budget`` (:func:`budget_dict`,
-    joined with the culled ledger), ``surface`` (the dict of ``Engine.surface()``).
+    joined with the culled ledger), ``surface`` (the dict of ``Engine.surface()``),
+    ``volume`` (the dict of ``Engine.volume()``).
 
     ``reduce``: a callable that sums a float64 vector over the ranks of a sharded
     trace, every rank calling alike: one exchange for the culled ledger; one for
     the budget, ``iterations`` rows of 13 and the (K, 4) tables; the map's three
-    tables in pieces of at most ``piece`` values (a comm's payload is an int32
+    tables, and the volume map's voxels with ``outside`` and ``segments`` behind
+    them, in pieces of at most ``piece`` values (a comm's payload is an int32
     count of float64) -- sizes that no rank's data changes.  Counts are exact in
     float64 and come back as int64."""
     out = {}
@@ -155,4 +179,14 @@ def read_ledgers(engine, reduce=None, iterations=None, piece=1 << 20):
             s = {"incident": tot[:m].copy(), "deposited": tot[m:2 * m].copy(),
                  "count": np.rint(tot[2 * m:]).astype(np.int64)}
         out["surface"] = s
+    if getattr(engine, "volume_on", False):
+        v = engine.volume()
+        if reduce is not None:
+            flat = np.concatenate((v["deposited"].ravel(), [v["outside"], float(v["segments"])]))
+            tot = np.empty_like(flat)
+            for lo in range(0, len(flat), piece):
+                tot[lo:lo + piece] = reduce(flat[lo:lo + piece])
+            v = dict(v, deposited=tot[:-2].reshape(v["shape"]).copy(), outside=float(tot[-2]),
+                     segments=int(np.rint(tot[-1])))
+        out["volume"] = v
     return out

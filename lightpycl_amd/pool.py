@@ -67,11 +67,15 @@ class TracePool:
 
     @staticmethod
     def _trace(e, origin, direction, power, max_ray_len, ior_env, iterations, tau, measured, min_ray_power=0.0,
-               power_budget=False, surface_map=False):
+               power_budget=False, surface_map=False, volume_map=None):
         p = np.asarray(power, np.float32).reshape(-1)
         e.set_min_power(min_ray_power)      # set for every batch: omitted = off
         e.set_budget(power_budget)          # likewise
         e.set_surface(surface_map)
+        if volume_map is None:
+            e.set_volume(None)
+        else:
+            e.set_volume(volume_map["lo"], volume_map["hi"], volume_map["shape"])
         e.set_rays(origin, direction, p, max_ray_len, ior_env)
         thr = (1.0 - float(tau)) * float(np.sum(p, dtype=np.float64))
         stats, (count, mesh_power) = e.run_local(int(iterations), thr)
@@ -83,7 +87,7 @@ class TracePool:
         return out
 
     def submit(self, origin, direction, power, max_ray_len=1e3, ior_env=1.0, iterations=16, tau=0.99,
-               measured=False, min_ray_power=0.0, power_budget=False, surface_map=False):
+               measured=False, min_ray_power=0.0, power_budget=False, surface_map=False, volume_map=None):
         """Queue one batch (origin/direction (n,4) float32 rows, power (n,)):
         traced to the reference's termination (``iterations``, dissipated
         fraction ``tau``, iterative_tracer.py:383-391).  ``min_ray_power`` > 0:
@@ -93,13 +97,16 @@ class TracePool:
         ``power_budget`` of the result, the dict of ``CL_Tracer.power_budget()``.
         ``surface_map=True``: the trace's surface map (Engine.set_surface) as
         ``surface`` of the result, the dict of ``Engine.surface()``.
+        ``volume_map=dict(lo=, hi=, shape=)``: the trace's volume map
+        (Engine.set_volume) as ``volume`` of the result, the dict of
+        ``Engine.volume()``.
         Returns a Future."""
         fut = cf.Future()
         with self._lock:
             j = self._next
             self._next = (self._next + 1) % len(self.engines)
         self._q[j].put((fut, (origin, direction, power, max_ray_len, ior_env, iterations, tau, measured,
-                                float(min_ray_power), bool(power_budget), bool(surface_map))))
+                                float(min_ray_power), bool(power_budget), bool(surface_map), volume_map)))
         return fut
 
     def close(self):
