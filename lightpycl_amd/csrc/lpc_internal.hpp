@@ -303,6 +303,8 @@ struct StageArgs {
     double *tmp;                      // [ntiles][LPC_MP_MAX] measured power per tile and measure mesh
     unsigned long long *gsum;         // per group of LPC_ST_GROUP tiles: counts (21 bits each), zero before
     uint32_t *tmask;                  // the walk's written-slot masks (only those slots are read), or NULL
+    uint32_t single;                  // != 0 (tmask set): waves of rays with at most one written slot each take
+    uint32_t refr;                    //   postproc_single; refr: the scene's refr_mask (lpc_math.hpp)
     uint32_t *tbox;                   // [ntiles][6] box of the tile's kept children origins (ord_f32 min xyz,
                                       //   max xyz), or NULL: the next population's coherence key box
     // power cutoff (the CUT instantiations only): see CompactArgs

@@ -1454,18 +1454,29 @@ __global__ __launch_bounds__(256) void k_filter_eval(int64_t n, const float *__r
 }
 
 // ---------------------------------------------------------------------------
-// k_shade: postproc + Fresnel for one ray per lane (exact arithmetic).
+// What follows postproc in the shading of ray r (origin O, direction D, power pw,
+// measured state meas_in): the destination and reflect_refract_rays.
+static __device__ __forceinline__ ShadeOut shade_tail(const ShadeArgs &A, f3 O, f3 D, float pw, int32_t meas_in,
+                                                      const PostOut &po, f3 &dest)
+{
+    dest = ray_dest(O, D, po.t_min);
+    auto tri = [&](int32_t idx, f3 &v0, f3 &v1, f3 &v2) {
+        const float *v = A.verts + (int64_t)idx * 9;
+        v0 = mk3(v[0], v[1], v[2]); v1 = mk3(v[3], v[4], v[5]); v2 = mk3(v[6], v[7], v[8]);
+    };
+    return shade(O, D, dest, pw, meas_in, po.hit_mesh, po.hit_idx, po.n1, po.n2, A.mat_type, A.ior,
+                 A.refl, A.diss, A.ior_env, tri);
+}
+
+// postproc of ray r over its slots.
 // touched (optional): bit j set for slots j < 64 that hold anything but the clean
 // state (max_ray_len, idx -1, count 0), noted as postproc reads them
 // KU > 0 (A.K <= KU): the ray's K slots are loaded up front into registers (one
 // memory round trip instead of one per mesh and loop).
 template <int KU = 0>
-static __device__ __forceinline__ ShadeOut shade_eval(const ShadeArgs &A, int64_t r, PostOut &po, f3 &dest,
-                                                      uint64_t *touched = nullptr, uint32_t lmask = 0xffffffffu)
+static __device__ __forceinline__ PostOut shade_post(const ShadeArgs &A, int64_t r, int32_t prev,
+                                                     uint64_t *touched = nullptr, uint32_t lmask = 0xffffffffu)
 {
-    const f3 O = mk3(A.in.ox[r], A.in.oy[r], A.in.oz[r]);
-    const f3 D = mk3(A.in.dx[r], A.in.dy[r], A.in.dz[r]);
-    const int32_t prev = A.in.pmid[r];
     const int64_t n = A.n;
     const unsigned long long k0 = slot_key(A.max_ray_len, -1);
     if constexpr (KU > 0) {
@@ -1491,7 +1502,7 @@ static __device__ __forceinline__ ShadeOut shade_eval(const ShadeArgs &A, int64_
         auto slot = [&](int32_t j, float &t, int32_t &c, int32_t &i) {
             t = slot_key_t(kr[j]); i = slot_key_idx(kr[j]); c = cr[j];
         };
-        po = postproc<KU>(A.K, prev, A.mat_type, A.max_ray_len, slot);
+        return postproc<KU>(A.K, prev, A.mat_type, A.max_ray_len, slot);
     } else {
         auto slot = [&](int32_t j, float &t, int32_t &c, int32_t &i) {
             // lmask: the slots a flush wrote (the others hold the clean state)
@@ -1501,16 +1512,18 @@ static __device__ __forceinline__ ShadeOut shade_eval(const ShadeArgs &A, int64_
             t = slot_key_t(k); i = slot_key_idx(k); c = A.sc[a];
             if (touched && j < 64 && (k != k0 || c != 0)) *touched |= 1ull << j;
         };
-        po = postproc(A.K, prev, A.mat_type, A.max_ray_len, slot);
+        return postproc(A.K, prev, A.mat_type, A.max_ray_len, slot);
     }
-    dest = ray_dest(O, D, po.t_min);
-    const int32_t meas_in = A.meas_in ? A.meas_in[r] : 0;
-    auto tri = [&](int32_t idx, f3 &v0, f3 &v1, f3 &v2) {
-        const float *v = A.verts + (int64_t)idx * 9;
-        v0 = mk3(v[0], v[1], v[2]); v1 = mk3(v[3], v[4], v[5]); v2 = mk3(v[6], v[7], v[8]);
-    };
-    return shade(O, D, dest, A.in.pw[r], meas_in, po.hit_mesh, po.hit_idx, po.n1, po.n2, A.mat_type, A.ior,
-                 A.refl, A.diss, A.ior_env, tri);
+}
+
+// k_shade: postproc + Fresnel for one ray per lane (exact arithmetic).
+template <int KU = 0>
+static __device__ __forceinline__ ShadeOut shade_eval(const ShadeArgs &A, int64_t r, PostOut &po, f3 &dest)
+{
+    const f3 O = mk3(A.in.ox[r], A.in.oy[r], A.in.oz[r]);
+    const f3 D = mk3(A.in.dx[r], A.in.dy[r], A.in.dz[r]);
+    po = shade_post<KU>(A, r, A.in.pmid[r]);
+    return shade_tail(A, O, D, A.in.pw[r], A.meas_in ? A.meas_in[r] : 0, po, dest);
 }
 
 template <int KU = 0>
@@ -1831,6 +1844,9 @@ static __device__ __forceinline__ int tile_tid()
 // record (six stores, taken before the cutoff) for k_budget_sum; with the surface
 // map on (lpc_trace_set_surface) a seventh, the hit triangle, for k_surface_sum;
 // with the volume map on (lpc_trace_set_volume) dest, for k_volume_sum.
+#ifndef LPC_SHADE_EMPTY_SKIP
+#define LPC_SHADE_EMPTY_SKIP 1            // compile-time A/B builds: 0 = every wave runs the kept children's reductions
+#endif
 template <int KU, bool DS, bool CUT = false, bool BUD = false>
 __global__ __launch_bounds__(LPC_ST_TILE) void k_shade_stage(StageArgs A)
 {
@@ -1859,19 +1875,56 @@ __global__ __launch_bounds__(LPC_ST_TILE) void k_shade_stage(StageArgs A)
     ShadeOut s;
     memset(&s, 0, sizeof(s));
     s.r_meas = -1; s.t_meas = -1;
+    // The ray and the walk's written-slot mask (K <= 32: only those slots are read,
+    // and the mask goes back to 0 with them) are loaded side by side, the slots
+    // behind the mask, and every store comes after the slots' loads: two round
+    // trips to memory ahead of the hit triangle's vertices.
+    uint32_t lm = 0xffffffffu;
+    const unsigned long long k0 = slot_key(S.max_ray_len, -1);
+    f3 O = mk3(0.0f, 0.0f, 0.0f), D = O;
+    int32_t prev = -2;
+    float pw = 0.0f;
     if (in) {
-        uint64_t touched = 0;
-        // the walk's written-slot mask (K <= 32): only those slots are read, and
-        // the mask goes back to 0 with them
-        uint32_t lm = 0xffffffffu;
-        if (A.tmask) {
-            lm = A.tmask[r];
-            if (lm) A.tmask[r] = 0u;
+        if (A.tmask) lm = A.tmask[r];
+        O = mk3(S.in.ox[r], S.in.oy[r], S.in.oz[r]);
+        D = mk3(S.in.dx[r], S.in.dy[r], S.in.dz[r]);
+        prev = S.in.pmid[r];
+        pw = S.in.pw[r];
+    }
+    // The single-slot path (A.single: masks present): a wave whose rays each wrote
+    // at most one slot reads that slot alone and takes postproc_single; a ray
+    // that needs postproc's second loop (its `generic`) sends the wave back.
+    bool single = false;
+    if (A.single) {
+        const uint32_t lk = lm & (S.K >= 32 ? 0xffffffffu : (1u << S.K) - 1u);      // (bits from K up are never read)
+        if (!any_lane(in && __popc(lk) > 1)) {
+            const int j0 = lk ? __builtin_ctz(lk) : 0;
+            unsigned long long k1 = k0;
+            int32_t c1 = 0;
+            bool generic = false;
+            if (in) {
+                if (lk) {
+                    const int64_t a = (int64_t)j0 * S.n + r;
+                    k1 = A.skey[a];
+                    c1 = A.scnt[a];
+                }
+                po = postproc_single(prev, A.refr, S.max_ray_len, j0, slot_key_t(k1), c1, slot_key_idx(k1), generic);
+            }
+            single = !any_lane(generic);
+            if (single && in && lm) A.tmask[r] = 0u;
+            if (single && in && (k1 != k0 || c1 != 0)) {    // the slot just read back to the clean state
+                const int64_t a = (int64_t)j0 * S.n + r;
+                A.skey[a] = k0;
+                A.scnt[a] = 0;
+            }
         }
-        s = shade_eval<KU>(S, r, po, dest, &touched, lm);
+    }
+    if (in && !single) {
+        uint64_t touched = 0;
+        po = shade_post<KU>(S, r, prev, &touched, lm);
+        if (A.tmask && lm) A.tmask[r] = 0u;
         // the slots just read back to the clean state: those a flush wrote (noted
         // while postproc read them; slots 64 and up are read again)
-        const unsigned long long k0 = slot_key(S.max_ray_len, -1);
         while (touched) {
             const int j = __builtin_ctzll(touched);
             touched &= touched - 1;
@@ -1885,11 +1938,12 @@ __global__ __launch_bounds__(LPC_ST_TILE) void k_shade_stage(StageArgs A)
             if (A.scnt[a] != 0) A.scnt[a] = 0;
         }
     }
+    if (in) s = shade_tail(S, O, D, pw, S.meas_in ? S.meas_in[r] : 0, po, dest);     // (a trace's rays: no meas_in)
     if constexpr (BUD) {
         // (the seventh array lies behind the sixth, at the records' stride; dest behind the seventh)
         if (in)
             budget_record(A.bud, (A.bud_tri & LPC_REC_TRI) ? (int32_t *)(A.bud.kt + A.cst) : nullptr,
-                          (A.bud_tri & LPC_REC_DEST) ? A.bud.kt + 2 * A.cst : nullptr, A.cst, dest, S, r, S.in.pw[r],
+                          (A.bud_tri & LPC_REC_DEST) ? A.bud.kt + 2 * A.cst : nullptr, A.cst, dest, S, r, pw,
                           po, s);
     }
     bool fR = in && s.r_meas == 0, fT = in && s.t_meas == 0;
@@ -1920,14 +1974,20 @@ __global__ __launch_bounds__(LPC_ST_TILE) void k_shade_stage(StageArgs A)
         pk += (double)s.t_pow;
         dm = fmaxf(dm, s.t_dir.x * s.t_dir.x + s.t_dir.y * s.t_dir.y + s.t_dir.z * s.t_dir.z);
     }
-    pk = wave_sum(pk);
-    dm = wave_max(dm);
+    // (a wave that keeps no child would reduce zeros and infinities: its sums are
+    // +0.0, 0.0f and the empty box as they stand)
+    const bool kept = !LPC_SHADE_EMPTY_SKIP || (bR | bT) != 0;
+    if (kept) {
+        pk = wave_sum(pk);
+        dm = wave_max(dm);
+    }
     if (A.tbox) {       // the kept children's origins (= dest): the next population's key box
         const bool kb = (fR || fT) && isfinite(dest.x) && isfinite(dest.y) && isfinite(dest.z);
         const float v[3] = {dest.x, dest.y, dest.z};
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const float lo = wave_red(kb ? v[k] : INFINITY, 0), hi = wave_red(kb ? v[k] : -INFINITY, 1);
+            float lo = INFINITY, hi = -INFINITY;
+            if (kept) { lo = wave_red(kb ? v[k] : INFINITY, 0); hi = wave_red(kb ? v[k] : -INFINITY, 1); }
             if (lane == 0) { s_bx[wv][k] = ord_f32(lo); s_bx[wv][3 + k] = ord_f32(hi); }
         }
     }

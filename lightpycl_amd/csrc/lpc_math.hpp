@@ -219,6 +219,46 @@ LPC_HD PostOut postproc(int32_t K, int32_t prev, const int32_t *mat_type, float 
     return o;
 }
 
+// Bit j (j < K, j < 32): mesh j is refractive (material 0 or 4), the meshes
+// postproc's second loop looks at.
+LPC_HD uint32_t refr_mask(int32_t K, const int32_t *mat_type)
+{
+    uint32_t m = 0;
+    for (int32_t j = 0; j < K && j < 32; ++j)
+        if (mat_type[j] == 0 || mat_type[j] == 4) m |= 1u << j;
+    return m;
+}
+
+// postproc of a ray whose only written slot is j0 < 32 (t0, c0, i0); every other
+// slot holds the clean state (max_ray_len, -1, 0).  refr: refr_mask of the scene.
+// A clean slot never wins the first loop (max_ray_len < t_min is false) and, with
+// its entering flag 1, never passes the second loop's min-max test; slot j0 passes
+// the max-min test with its own t0 and leaves t_min and n2 as the first part set
+// them.  What remains is a clean refractive slot j != j0 passing the max-min test,
+// max_ray_len <= t0 + EPSILON in float (.cl:204): it would take the hit over
+// (t_min = max_ray_len, n2 = j).  Then `generic` is set and the result is not to
+// be used: the caller runs postproc.  generic is set in exactly the cases where
+// the two differ.
+LPC_HD PostOut postproc_single(int32_t prev, uint32_t refr, float max_ray_len, int32_t j0, float t0,
+                               int32_t c0, int32_t i0, bool &generic)
+{
+    LPC_EXACT
+    const float EPSILON = 0.000001f * max_ray_len;
+    PostOut o;
+    o.hit_mesh = -1; o.hit_idx = -1; o.n1 = -1; o.n2 = -1; o.entering = -1;
+    o.t_min = max_ray_len;
+    generic = false;
+    if (t0 < max_ray_len) {                                              // .cl:127-135 (a count with a clean key: no hit)
+        o.hit_mesh = j0; o.hit_idx = i0; o.t_min = t0;
+        const int32_t entering = 1 - (c0 % 2);                           // .cl:142
+        o.entering = entering;
+        if (entering == 1) { o.n1 = (prev == -2 || prev == -1) ? -1 : prev; o.n2 = j0; }   // .cl:145-177
+        else { o.n1 = j0; o.n2 = -1; }
+        generic = max_ray_len <= t0 + EPSILON && (refr & ~(1u << j0)) != 0;
+    }
+    return o;
+}
+
 // dest = o + d * t_min (.cl:237)
 LPC_HD f3 ray_dest(f3 O, f3 D, float t) { LPC_EXACT return add3(O, scl3(D, t)); }
 

@@ -158,6 +158,7 @@ struct Scene {
     int64_t n_slivers = 0, n_thin = 0;               // ... of them thin triangles (thin_axis, k = 1)
     std::vector<int32_t> slot_run, meas_meshes;
     bool mat_passive = false;                       // no material can raise a ray's power (lpc_scene_upload)
+    uint32_t refr = 0;                              // refr_mask: the refractive meshes among the first 32
     float box_lo[3] = {0, 0, 0}, box_scale[3] = {1, 1, 1};
     double scene_scale = 1.0, dcap = 16.0;           // half diagonal of the scene box (filter h), the filter's Dcap
     std::map<std::vector<int32_t>, PieceTable> ptabs;   // by the hierarchy level each live run is cut at
@@ -194,6 +195,8 @@ struct Knobs {
                                                     //   own (A/B and test hook; the same PacketRec bits)
     bool roots_lds = true;                          // LPC_ROOTS_LDS: k_roots_s asks for the LDS its batch's records
                                                     //   need; 0 = for a full batch's (A/B hook)
+    bool shade_fast = true;                         // LPC_SHADE_FAST: k_shade_stage's single-slot path; 0 = every wave
+                                                    //   takes postproc (A/B and test hook; the same bits)
     double dcap_init = 16.0;                        // LPC_DCAP_MILLI / 1000 (tests: a rebuild inside a trace)
     int spill_budget = 20;                          // LPC_BUDGET: node visits before a wave hands its work over (0 off)
     int64_t spill_large_per_tri = 16;               // LPC_LARGE_PER_TRI
@@ -1576,6 +1579,7 @@ int lpc_open(int device, lpc_handle **out)
     k.bsort = env_int("LPC_BSORT", k.bsort) != 0;
     k.packet_fold = env_int("LPC_PACKET_FOLD", k.packet_fold) != 0;
     k.roots_lds = env_int("LPC_ROOTS_LDS", k.roots_lds) != 0;
+    k.shade_fast = env_int("LPC_SHADE_FAST", k.shade_fast) != 0;
     k.dcap_init = (double)env_int("LPC_DCAP_MILLI", 16000) / 1000.0;
     k.spill_budget = (int)env_int("LPC_BUDGET", k.spill_budget);
     k.spill_large_per_tri = env_int("LPC_LARGE_PER_TRI", k.spill_large_per_tri);
@@ -1682,6 +1686,7 @@ int lpc_scene_upload(lpc_handle *h, int32_t tri_count, const float *v0, const fl
     HIPCHK(h, hipMemcpy(sc.d_live.p, live.data(), (size_t)K * 4, hipMemcpyHostToDevice));
     sc.meas_meshes.clear();
     for (int32_t j = 0; j < K; ++j) if (mat_type[j] == 3) sc.meas_meshes.push_back(j);
+    sc.refr = lpc::refr_mask(K, mat_type);
     // passive materials: the children of a ray never carry more power than it
     // (refractive: R, T = 1 - R in [0, 1] for finite positive indices,
     // .cl:313-326; mirror: P R with 0 <= R <= 1, .cl:443 -- a negative R flips the
@@ -2926,6 +2931,8 @@ static int enqueue_fused_chunk(lpc_handle *h, const IterPlan &I, const RaysIn &i
     const GroupWords::Turn gt = h->groups.turn(ng);     // this launch's k_shade_stage adds into its first ng groups
     G.gsum = gs + gt.cur;
     G.tmask = tmask;
+    G.single = tmask && h->knobs.shade_fast ? 1u : 0u;
+    G.refr = h->scene.refr;
     G.tbox = I.want_box ? (uint32_t *)h->w_tbox.p : nullptr;
     G.cut = h->led.min_power; G.tcc = (uint32_t *)I.L.CS.cc; G.tcp = (double *)I.L.CS.cp;
     G.bud = I.L.R; G.bud_tri = I.L.rec_mask();          // (the records' stride is cst: both are ws_rays)
