@@ -176,6 +176,69 @@ class RefKernels:
                     t_origin=h(to), t_dir=h(td), t_pow=h(tp), t_meas=h(tm), isect_min_ray_len=h(tmin),
                     isects_count=h(cnt), isect_idx_tmp=h(itmp))
 
+    # -- one kernel each, on buffers the caller made up ----------------------------
+    def postproc(self, scene, origin, direction, prev, tmin, cnt, itmp, max_ray_len):
+        """intersect_postproc alone on caller-supplied [ray][mesh] scratch (tmin, cnt,
+        itmp: (n, K)), with the argument list ``bounce`` passes.  Returns dest, n1,
+        n2, entering, isect_mid, isect_idx; entering starts as 0 (the kernel writes
+        it only on a hit, iterative_tracer.py:230)."""
+        if getattr(self, "scene", None) is not scene:
+            self.upload_scene(scene)
+        n = int(np.asarray(prev).shape[0])
+        K = int(scene.mesh_count)
+        mrl = np.float32(max_ray_len)
+        n_pad = -(-n // BLOCK) * BLOCK
+        F, I = np.float32, np.int32
+        o = self._dev(np.asarray(origin, F).reshape(-1, 4), n_pad)
+        d = self._dev(np.asarray(direction, F).reshape(-1, 4), n_pad)
+        pm = self._dev(np.asarray(prev, I).reshape(-1), n_pad, fill=-2)
+        t = self._dev(np.asarray(tmin, F).reshape(n, K), n_pad, fill=mrl)      # padding rows: no hit
+        c = self._dev(np.asarray(cnt, I).reshape(n, K), n_pad)
+        it = self._dev(np.asarray(itmp, I).reshape(n, K), n_pad)
+        dest = self._zeros((n_pad, 4), F)
+        ent, imid, iidx, n1, n2 = (self._zeros(n_pad, I) for _ in range(5))
+        self._launch("intersect_postproc", n_pad, [
+            ("p", o), ("p", d), ("p", dest), ("p", pm), ("p", n1), ("p", n2), ("p", ent), ("p", imid),
+            ("p", iidx), ("p", self.v0), ("p", self.v1), ("p", self.v2), ("p", self.mid), ("p", self.typ),
+            ("p", t), ("p", c), ("p", it), ("i", K), ("i", n), ("f", mrl)])
+        h = lambda x: x.cpu().numpy()[:n]
+        return dict(dest=h(dest), n1=h(n1), n2=h(n2), entering=h(ent), isect_mid=h(imid), isect_idx=h(iidx))
+
+    def reflect_refract(self, scene, origin, dest, direction, power, meas, ent, n1, n2, imid, iidx, ior_env,
+                        max_ray_len):
+        """reflect_refract_rays alone on caller-supplied postproc outputs, with the
+        argument list ``bounce`` passes.  Returns pow and meas as the kernel left
+        them in place, and the two children.  Padding rows hit nothing."""
+        if getattr(self, "scene", None) is not scene:
+            self.upload_scene(scene)
+        n = int(np.asarray(imid).shape[0])
+        K = int(scene.mesh_count)
+        mrl = np.float32(max_ray_len)
+        n_pad = -(-n // BLOCK) * BLOCK
+        F, I = np.float32, np.int32
+        o = self._dev(np.asarray(origin, F).reshape(-1, 4), n_pad)
+        e = self._dev(np.asarray(dest, F).reshape(-1, 4), n_pad)
+        d = self._dev(np.asarray(direction, F).reshape(-1, 4), n_pad)
+        pw = self._dev(np.asarray(power, F).reshape(-1), n_pad)
+        ms = self._dev(np.asarray(meas, I).reshape(-1), n_pad)
+        en = self._dev(np.asarray(ent, I).reshape(-1), n_pad)
+        a1 = self._dev(np.asarray(n1, I).reshape(-1), n_pad, fill=-1)
+        a2 = self._dev(np.asarray(n2, I).reshape(-1), n_pad, fill=-1)
+        im = self._dev(np.asarray(imid, I).reshape(-1), n_pad, fill=-1)
+        ii = self._dev(np.asarray(iidx, I).reshape(-1), n_pad)
+        ro, rd, to, td = (self._zeros((n_pad, 4), F) for _ in range(4))
+        rp, tp = self._zeros(n_pad, F), self._zeros(n_pad, F)
+        rm, tm = self._zeros(n_pad, I), self._zeros(n_pad, I)
+        self._launch("reflect_refract_rays", n_pad, [
+            ("p", o), ("p", e), ("p", d), ("p", pw), ("p", ms), ("p", en), ("p", a1), ("p", a2),
+            ("p", ro), ("p", rd), ("p", rp), ("p", rm), ("p", to), ("p", td), ("p", tp), ("p", tm),
+            ("p", im), ("p", ii), ("p", self.v0), ("p", self.v1), ("p", self.v2), ("p", self.mid),
+            ("p", self.typ), ("p", self.ior), ("p", self.refl), ("p", self.diss), ("f", ior_env),
+            ("i", K), ("i", n), ("f", mrl)])
+        h = lambda x: x.cpu().numpy()[:n]
+        return dict(pow=h(pw), meas=h(ms), r_origin=h(ro), r_dir=h(rd), r_pow=h(rp), r_meas=h(rm),
+                    t_origin=h(to), t_dir=h(td), t_pow=h(tp), t_meas=h(tm))
+
     # -- projections, iterative_tracer.py:503-562 --------------------------------
     def project(self, pos, pwr, mode="angular", rot=None, pivot=None):
         n = int(np.asarray(pwr).reshape(-1).shape[0])
